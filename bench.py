@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- MCTS simulations/sec of the batched self-play engine (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
 
 N > 1 is served either way the driver may start it: under `python -m torch.distributed.run --nproc-per-node N bench.py
 --gpus N ...` (RANK / WORLD_SIZE in the environment), or as plain `python bench.py --gpus N`, in which case this process
@@ -16,10 +16,13 @@ record).  Workload at N = 1 = BASELINE.json configs[1]: CartPole-v1 shaped synth
 pin).  Inputs (weights, env state, trees) are resident in HBM before the timed region.  N > 1: each rank owns 4096 envs
 (weak scaling) and the finished K-step trajectory chunk is gathered to rank 0 over RCCL inside the timed region.
 
-Timing: after W warm-up steps, R blocks of EXACTLY K steps are timed, each bracketed by barrier + torch.cuda.synchronize
-on both sides, the block time being the MAX over ranks; R is chosen so that the timed region is about 0.5 s or more
-(one 10 ms block is at the mercy of a host hiccup).  `value` and `ms_per_step` come from the MEDIAN block; the spread
-is in `timing`.
+Timing: after PRIME_STEPS (256) priming steps and W warm-up steps, EXACTLY K env steps are timed as one block, bracketed
+by barrier + torch.cuda.synchronize on both sides, the block time being the MAX over ranks; `value` and `ms_per_step` come
+from that block.  The number of steps the engine has played is therefore fixed by the arguments, and so is everything
+it computed (seeded envs, trees and weights): --dump-outputs DIR writes what the timed path returned for its last step (the
+trajectory record of every env, as a caller of play_games_grouped / the N > 1 gather receives it) to DIR/<field>.npy, so
+that two builds can be compared output for output.  K sets the size of the timed window: a window of a few ms measures
+the host as much as the GPU, so pass a K that times a second or more (the headline runs at ~0.4 ms per step).
 
 The JSON line also carries, for every workload,
   roofline     -- the dominant kernel's algorithmic bytes (SURVEY.md 8d formula evaluated on this run's own level
@@ -281,6 +284,31 @@ def cpu_baseline_vision(wl, weights_path, seconds_target=12.0):
                        f"process {one:.0f} simulations/s")
 
 
+PRIME_STEPS = 256                  # untimed env steps before the warm-up (see main)
+DUMP_BYTES = 63 * 10 ** 6          # array bytes of a --dump-outputs directory; with the .npy headers it stays under 64 MB
+
+
+def dump_outputs(outdir, fields):
+    """fields: name -> [envs, ...] device tensor of the last timed step.  Writes <outdir>/<name>.npy for each (float64 record
+    fields, float32 frames as they are).  Beyond DUMP_BYTES the same fixed, seeded sample of envs is taken from every field,
+    and its indices go to env_index.npy."""
+    import numpy as np
+    import torch
+    fields = {k: v for k, v in fields.items() if v is not None}
+    n = next(iter(fields.values())).shape[0]
+    per_env = sum(v[0].numel() * v.element_size() for v in fields.values())
+    if n * per_env > DUMP_BYTES:
+        keep = DUMP_BYTES // (per_env + 8)
+        idx = np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+        fields = {k: v[torch.from_numpy(idx).to(v.device)] for k, v in fields.items()}
+        fields["env_index"] = torch.from_numpy(idx.astype(np.float64))
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in fields.items():
+        a = v.cpu().numpy()
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        np.save(os.path.join(outdir, k + ".npy"), a)
+
+
 class ReplaySink:
     """What ReplayBuffer.save_game does with a game (replay_buffer.py:109-137), restated as the bench's sink: evict beyond the
     window, make_priority(td_steps) -> per-position and per-game priorities, append, count positions; games that were not
@@ -335,7 +363,10 @@ def self_launch(args, argv):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="env steps per timed block (default 16; 64 with --end-to-end)")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="env steps timed (default 16; 64 with --end-to-end, where the timed block is --pipeline iterations of K "
+                         "steps).  The default times ~6 ms of the headline, too short for a stable number: pass a K that times a "
+                         "second or more (~2500 on the headline)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cartpole_mlp_4096x50", choices=sorted(WORKLOADS))
     ap.add_argument("--envs", type=int, default=None, help="envs per GPU (default: the workload's)")
@@ -350,9 +381,11 @@ def main():
                     help="independent env groups per GPU, each on its own HIP stream (0 = 2 groups from 262 144 envs on -- "
                          "one group's tree kernel overlaps the other's network kernel: +6..14 %% measured -- else 1)")
     ap.add_argument("--min-timed-seconds", type=float, default=10.0,
-                    help="repeat the K-step block until this much is timed (default 10 s: ~1400 blocks of the headline workload, so "
-                         "that the timed region is the larger part of the command's run time)")
-    ap.add_argument("--max-blocks", type=int, default=4000)
+                    help="accepted for the command lines of tools/; the timed region is --steps env steps whatever this says")
+    ap.add_argument("--max-blocks", type=int, default=4000, help="cap on the blocks of an `also` line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned for its last step to DIR/<field>.npy (float64 "
+                         "record fields, float32 frames; a fixed, seeded sample of envs beyond 64 MB, their indices in env_index.npy)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=5.0, help="wall-clock budget of the cpu_baseline sample (all host cores)")
     ap.add_argument("--end-to-end", action="store_true",
                     help="time selfplay.self_play_iteration, the function learning_cycle calls (self_play.py:245-271): K env steps, the "
@@ -406,6 +439,10 @@ def main():
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 64 if args.end_to_end else 16
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.end_to_end:
+        ap.error("--dump-outputs writes the search path's trajectory records; --end-to-end times Game records instead")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -558,16 +595,19 @@ def main():
     gather_mode = xch.mode if xch is not None else {"kind": None}
 
     def play_and_gather(n):
-        """n env steps of every group; with N > 1 in slices, each slice's rows handed to the overlapped gather."""
+        """n env steps of every group; with N > 1 in slices, each slice's rows handed to the overlapped gather.  Returns
+        (chunks, gathered): gathered = (records, frames | None) of the whole job on rank 0 when N > 1, else None."""
         if xch is None:
-            return sp.play_games_grouped(groups, args.temperature, n)
-        return xch.run(n)[0]
+            return sp.play_games_grouped(groups, args.temperature, n), None
+        return xch.run(n)
+
+    last = {}                                                 # what the timed block's play_and_gather returned
 
     def timed_block():
         """EXACTLY K steps (+ the trajectory gather when N > 1) between two barrier + synchronize pairs; max over ranks."""
         barrier()
         t0 = time.perf_counter()
-        play_and_gather(args.steps)
+        last["chunks"], last["gathered"] = play_and_gather(args.steps)
         barrier()
         dt_block = max_over_ranks(time.perf_counter() - t0)
         if tg is not None and tg.exposed_gather_ms() is not None:
@@ -614,8 +654,8 @@ def main():
                 e2e_parts.append((n_games // max(1, args.pipeline), sink.positions // max(1, args.pipeline)))
             return dt_block
 
-    # one priming step outside everything: code-object upload, LDS opt-in and allocator warm-up are initialisation, not
-    # part of a step (a run with --warmup 0 would otherwise time them)
+    # the first priming step, outside everything: code-object upload, LDS opt-in and allocator warm-up are initialisation,
+    # not part of a step (a run with --warmup 0 would otherwise time them)
     sp.play_games_grouped(groups, args.temperature, 1)
     torch.cuda.synchronize(dev)
     # Python's cyclic collector pauses the host for 30-50 ms when a full collection falls into the loop (torch keeps
@@ -625,17 +665,29 @@ def main():
     gc.collect()
     gc.freeze()
     gc.disable()
+    # the rest of the PRIME_STEPS priming steps, back to back with the warm-up and the timed block: the first few hundred
+    # steps of a run are slower than the steady state (headline at --steps 20 --warmup 5: 492-499 M simulations/s with one
+    # priming step, 494-516 M with 256, 519-521 M over a 1 s window -- tools/priming_ab.sh, profiles/r07_a_priming_ab.txt).
+    # A fixed count, so that the steps played -- and everything they compute -- follow from the arguments alone.
+    for s0 in range(1, PRIME_STEPS, T):
+        sp.play_games_grouped(groups, args.temperature, min(T, PRIME_STEPS - s0))
     # W untimed warm-up steps (with N > 1 the first grouped send / recv builds the RCCL communicators here, outside the timed
     # region; if that first overlapped exchange RAISES, ChunkExchange.warm_up falls back to the plain gather)
     if xch is not None:
         chunks = xch.warm_up(max(1, args.warmup))[0]
     else:
-        chunks = play_and_gather(args.warmup)
+        chunks = play_and_gather(args.warmup)[0]
     torch.cuda.synchronize(dev)
-    first = timed_block()                                      # block 1 (timed like the others; also sizes R)
-    R = int(min(args.max_blocks, max(1, np.ceil(args.min_timed_seconds / max(first, 1e-6)))))
-    blocks = [first] + [timed_block() for _ in range(R - 1)]
-    dt = float(np.median(blocks))
+    dt = timed_block()
+    if args.dump_outputs and rank == 0:
+        if multi:
+            records, frames = last["gathered"]
+        else:
+            records, frames = rows(last["chunks"], "data", 0, args.steps), rows(last["chunks"], "obs", 0, args.steps)
+        fields = groups[0].chunk.fields(records[-1])
+        if frames is not None:
+            fields["observation"] = frames[-1]
+        dump_outputs(args.dump_outputs, fields)
     per_rank_rate, ranks_seen, gather_ms = None, None, None
     if multi:                                                  # every rank's own rate of its last block, for the record
         barrier()
@@ -706,12 +758,9 @@ def main():
            "warmup": args.warmup, "ms_per_step": 1e3 * dt / block_steps, "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "f32 (tree values, heads) + f64 (pUCT scores, root priors) + i32 (counts)",
            "data": data_note, "config": config,
-           "timing": {"blocks": R, "steps_per_block": block_steps, "block_ms_median": 1e3 * dt,
-                      "block_ms_min": 1e3 * float(np.min(blocks)), "block_ms_max": 1e3 * float(np.max(blocks)),
-                      "block_ms_p10_p90": [1e3 * float(np.percentile(blocks, 10)), 1e3 * float(np.percentile(blocks, 90))],
-                      "timed_region_s": float(np.sum(blocks)),
-                      "rule": "value and ms_per_step from the median block; every block is K steps between barrier + "
-                              "synchronize pairs, max over ranks"}}
+           "timing": {"priming_steps": PRIME_STEPS, "blocks": 1, "steps_per_block": block_steps, "block_ms": 1e3 * dt,
+                      "rule": "value and ms_per_step from one block of exactly K steps between barrier + synchronize "
+                              "pairs, max over ranks"}}
     if args.end_to_end and rank == 0:
         # where one iteration's time goes (one extra iteration, each part between synchronisations)
         torch.cuda.synchronize(dev)
@@ -734,7 +783,7 @@ def main():
                              "sink": "bench.ReplaySink.save_game per game: make_priority(td_steps=50) + priority / position "
                                      "bookkeeping (replay_buffer.py:109-137 without its O(buffer) re-normalisation per save)",
                              "note": "the three parts of ONE extra iteration, each between synchronisations; `value` is the whole "
-                                     "self_play_iteration call (env.reset + play + records + save), median block"}
+                                     "self_play_iteration call (env.reset + play + records + save), timed block"}
     if per_rank_rate is not None:
         out["per_rank_simulations_per_s"] = per_rank_rate
         out["timing"]["gather_ms_median"] = gather_ms
@@ -941,8 +990,8 @@ def main():
         out["cpu_baseline"] = cpu_baseline
 
     def also_line(name, seconds, steps=16):
-        """One of the other single-GPU BASELINE configs, timed like the headline (blocks of `steps` env steps between
-        synchronisations, median block) for ~`seconds`, + the dominant kernel's launch time and algorithmic-bytes fraction."""
+        """One of the other single-GPU BASELINE configs, timed in blocks of `steps` env steps between synchronisations
+        (median block) for ~`seconds`, + the dominant kernel's launch time and algorithmic-bytes fraction."""
         w = dict(WORKLOADS[name])
         Bw = w["envs"]
         wp = os.path.join(ROOT, "tests", "golden", w["weights"])

@@ -170,21 +170,60 @@ def test_batch1_inference_api_reproduces_reference_outputs(name, wname):
         np.testing.assert_allclose(v, c["tape_value"][s], rtol=1e-4, atol=5e-4)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/model_checkpoint"), reason="reference checkpoints not present")
-def test_loads_the_reference_checkpoint_files_without_the_reference_source():
-    """The real 421 checkpoint (whole-module pickles naming neural_network_mlp_model.*) loads through the
-    compatibility classes and carries exactly the weights of the committed array fixture."""
+# module attributes that torch releases newer than the one the reference trained with add to every pickled nn.Module
+# (torch.nn.Module.__setstate__ fills them in when a checkpoint lacks them)
+_NEWER_MODULE_KEYS = ("_backward_pre_hooks", "_forward_hooks_with_kwargs", "_forward_hooks_always_called",
+                      "_forward_pre_hooks_with_kwargs", "_state_dict_pre_hooks", "_load_state_dict_post_hooks")
+
+
+def test_loads_the_reference_checkpoint_files_without_the_reference_source(tmp_path):
+    """The 421 checkpoint in the reference's file layout AS AN OLDER TORCH WROTE IT (muzero_model.py:911-996): six
+    whole-module pickles naming neural_network_mlp_model.* whose module state lacks the hook dictionaries newer torch
+    releases add, an encoder without the onehot_argmax submodule, and an init_variables.json whose training settings differ
+    from what save_model writes.  Built here from the committed array fixture, it loads through the compatibility classes
+    while no module of the reference is importable, carries exactly those weights and evaluates like the array model."""
+    import copy
+    import json
     import sys
     model = _pkg("model")
-    assert "/root/reference" not in sys.path
-    m = model.Muzero.from_checkpoint("/root/reference/model_checkpoint", tag=421)
+    src = model.Muzero.from_arrays(os.path.join(gu.GOLDEN, "weights_ckpt421.npz"))
+    src.random_tag = 421
+    with model._compat_modules_bound(force=True):
+        for f in model._FUNCS:
+            mod = copy.deepcopy(getattr(src, f + "_function"))
+            if f == "encoder":
+                del mod.onehot_argmax
+            for sub in mod.modules():
+                for k in _NEWER_MODULE_KEYS:
+                    sub.__dict__.pop(k, None)
+            torch.save(mod, tmp_path / f"421_muzero_{f}_function.pt")
+    iv = dict(src.init_variables(), lr_scheduler="cosineannealinglr", num_of_epoch=10000, priority_scale=0.5)
+    (tmp_path / "421_muzero_init_variables.json").write_text(json.dumps(iv))
+    for f in model._FUNCS:
+        raw = open(tmp_path / f"421_muzero_{f}_function.pt", "rb").read()
+        assert b"neural_network_mlp_model" in raw and f"{f.capitalize()}_function".encode() in raw, f
+        assert not any(re.search(rb"(?<![A-Za-z])" + k.encode(), raw) for k in _NEWER_MODULE_KEYS), f   # (whole keys)
+    assert b"StraightThroughEstimator" not in open(tmp_path / "421_muzero_encoder_function.pt", "rb").read()
+    assert "neural_network_mlp_model" not in sys.modules
+    m = model.Muzero.from_checkpoint(str(tmp_path), tag=421)
+    assert "neural_network_mlp_model" not in sys.modules                # bound for the load only
     assert type(m.dynamics_function).__module__ == "neural_network_mlp_model"
+    assert all(model._is_compat_class(type(getattr(m, f + "_function"))) for f in model._FUNCS)
+    assert (m.extra["lr_scheduler"], m.extra["num_of_epoch"], m.extra["priority_scale"]) == ("cosineannealinglr", 10000, 0.5)
     got = model.mlp_arrays_from_modules(m.representation_function, m.prediction_function, m.afterstate_prediction_function,
                                         m.afterstate_dynamics_function, m.dynamics_function)
     z = np.load(os.path.join(gu.GOLDEN, "weights_ckpt421.npz"))
     for k, v in got.items():
         assert np.array_equal(v.numpy(), z[k]), k
     assert (m.observation_dimension, m.action_dimension, m.state_dimension) == (4, 2, 31)
+    # the restored modules run: hooks dictionaries back in place, same numbers as the array model
+    obs = torch.from_numpy(np.random.RandomState(0).uniform(-0.05, 0.05, (5, 4)).astype(np.float32))
+    with torch.no_grad():
+        h, h_src = m.representation_function(obs), src.representation_function(obs)
+        assert torch.equal(h, h_src)
+        for a, b in zip(m.prediction_function(h), src.prediction_function(h_src)):
+            assert torch.equal(a, b)
+        assert torch.equal(m.encoder_function(obs)[1], src.encoder_function(obs)[1])
 
 
 def test_cli_argv_and_config_surface():

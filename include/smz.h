@@ -33,6 +33,7 @@ extern "C" {
 
 #define SMZ_ABI_VERSION 1
 #define SMZ_MAX_ACTIONS 32 /* action_dimension limit of this build (per-lane scratch is sized by it) */
+#define SMZ_MAX_PLAYER_CYCLE 32 /* longest turn cycle smz_set_players accepts */
 #define SMZ_MT_WORDS 624   /* MT19937 state words per tree */
 
 typedef enum {
@@ -128,6 +129,16 @@ int smz_rng_restore(smz_handle *h, smz_stream stream);
  * (self_play.py:79): a finished game stops consuming simulations.  The array is read when the kernels run, so the
  * env-step kernel may clear entries on the same stream (smz_cartpole_step_ctl). */
 int smz_set_active(smz_handle *h, const uint8_t *active_dev);
+/* Multi-player search (Player_cycle, mcts:38-72, and the backup sign of mcts:299-308).  The turn cycle has n_cycle entries
+ * (1 .. SMZ_MAX_PLAYER_CYCLE) with the values cycle_values_host[0 .. n_cycle) -- range(number_of_player), or the numbers of a
+ * custom loop "1>2>1>3".  root_player_dev [B] i32 holds each tree's root player index (taken mod n_cycle; NULL: 0 for every
+ * tree); like smz_set_active it is read when the kernels run, so the caller may rewrite it between (graph) replays.  A node
+ * at depth d plays cycle index (root + 2 (d >> 2) + ((d & 3) != 0)) mod n_cycle; the backup adds -value instead of value to
+ * the value_sum of every node whose cycle VALUE differs from the root's.  Selection, the random draws and the value chain
+ * are unchanged.  n_cycle > 1 selects the multi-player step-wise kernels (smz_expand_backup / smz_expand_backup_select);
+ * the single-launch searches (smz_search_mlp*, smz_search_vision*) then fail with SMZ_ERR_INVALID.  n_cycle = 1 restores
+ * the single-player search (cycle_values_host may then be NULL). */
+int smz_set_players(smz_handle *h, int n_cycle, const float *cycle_values_host, const int32_t *root_player_dev);
 /* Large batches: the row moves of a simulation round can be left to the network kernel.  When ids_dev is set, every
  * selection (smz_select, smz_expand_backup_select) also writes, per tree, the node ids of the selected leaf and of its
  * parent to ids_dev [B][2] i32 ({-1, -1} for a tree switched off with smz_set_active); a network kernel then reads the

@@ -75,6 +75,10 @@ struct Params {
                                   // threshold (chance_threshold2).  Block of a decision-flagged node: float32 y[2], the children's
                                   // reward + discount * value_sum / visits as of their last backup (value_term)
     int32_t ry_off;               // ... and y[A] of the root's children at this word of the root block (-1: no room, not kept)
+    // multi-player backup (smz_set_players; read only by the MP instantiations of the step-wise expansion + backup)
+    const int32_t *root_player;   // [B] or nullptr (0): index of the player at each tree's root, taken mod n_cycle
+    const uint32_t *player_neg;   // [n_cycle]: bit j of entry r set iff the player j turns after root player r differs from it
+    int32_t n_cycle;              // turn-cycle length L (<= 32); > 1 selects the MP instantiations
 };
 #ifdef SMZ_NO_MASK
 __device__ inline bool tree_active(const Params &, int) { return true; }
@@ -990,7 +994,10 @@ __device__ inline void store_value_term(const Params &P, uint32_t *tb, int b, in
 // ---------------------------------------------------------------------------------------------------------------
 // EXPAND_ONLY: stop after the expansion and return the leaf reward through *leaf_reward_out -- the caller runs the
 // backup with backup_levels_lanes (several lanes per tree).
-template <int MAXA, int KS, bool EXPAND_ONLY = false, bool THR = false, bool YV = false, class RNG = Rng, class REC = const uint4 *>
+// MP: the multi-player backup of mcts:299-308 -- value_sum gains -value at every path node whose player (cycle value) differs
+// from the root's; the visit count, the value chain and the MinMax update (of the signed value_sum) are as without it.
+template <int MAXA, int KS, bool EXPAND_ONLY = false, bool THR = false, bool YV = false, bool MP = false, class RNG = Rng,
+          class REC = const uint4 *>
 __device__ inline int expand_backup_tree(const Params &P, int tree, RNG &rng, TreeHdr &h, const float *policy_row,
                                          float reward, float value, REC rec, float *leaf_reward_out = nullptr) {
     static_assert(!THR || KS == 2, "stored chance thresholds: two children per block");
@@ -1067,6 +1074,17 @@ __device__ inline int expand_backup_tree(const Params &P, int tree, RNG &rng, Tr
     // ---- backup, leaf -> root: stores only -----------------------------------------------------------------------
     float v = value;
     float mn = h.mn, mx = h.mx;
+    // MP: node at depth d plays turn inc(d) = 2 (d >> 2) + ((d & 3) != 0) after the root (the children of a decision node
+    // share its player, every other child moves on one); `pj` = inc(d) mod L walks up with the records (record i: depth i + 1)
+    uint32_t neg = 0u;
+    int pj = 0;
+    if constexpr (MP) {
+        const int L = P.n_cycle;
+        int r = P.root_player ? P.root_player[tree] % L : 0;
+        if (r < 0) r += L;
+        neg = P.player_neg[r];
+        pj = (2 * (len >> 2) + ((len & 3) != 0)) % L;
+    }
     for (int i0 = len - 1; i0 >= 0; i0 -= CH) {
         uint4 r4[CH];
 #pragma unroll
@@ -1079,7 +1097,13 @@ __device__ inline int expand_backup_tree(const Params &P, int tree, RNG &rng, Tr
                 const int cnt = (b == 0) ? A : K;
                 uint32_t *np = block_ptr(P, tb, b) + 2 * sl;
                 const float r = (i0 - q == len - 1) ? leaf_reward : __uint_as_float(e4.w);
-                const float nvs = __uint_as_float(e4.z) + v;
+                float sv = v;
+                if constexpr (MP) {
+                    if ((neg >> pj) & 1u) sv = -v;
+                    pj -= ((i0 - q + 1) & 3) <= 1;       // inc(d - 1) = inc(d) - 1 iff d & 3 is 0 or 1
+                    if (pj < 0) pj += P.n_cycle;
+                }
+                const float nvs = __uint_as_float(e4.z) + sv;
                 const int nvc = (int)e4.y + 1;
                 *reinterpret_cast<uint2 *>(np) = make_uint2((uint32_t)nvc, __float_as_uint(nvs));     // (visit, value_sum)
                 const float qv = nvs / (float)nvc;

@@ -480,9 +480,10 @@ __global__ void __launch_bounds__(kWave) k_root_init(Params P, const float *hidd
 }
 #endif
 
+// (always inlined: with the multi-player kernels beside them, the wide buckets' fused kernels would otherwise call it)
 template <int MAXA, int KS, class RNG>
-__device__ inline void select_phase(const Params &P, int tree, bool valid, RNG &rng, TreeHdr &h, const double *pbc_lds,
-                                    float *parent_hidden, int32_t *last_action, uint8_t *branch, float *mlp_input) {
+__device__ __forceinline__ void select_phase(const Params &P, int tree, bool valid, RNG &rng, TreeHdr &h, const double *pbc_lds,
+                                             float *parent_hidden, int32_t *last_action, uint8_t *branch, float *mlp_input) {
     Leaf L = {0, 0, 0, 0};
     unsigned n_dec = 0, n_chance = 0, n_children = 0;
     if (valid) {
@@ -570,6 +571,51 @@ __global__ void __launch_bounds__(kWave, MAXA > 16 ? 1 : SMZ_EB_WAVES) k_expand_
         h = P.hdr[tree];
         leaf = expand_backup_tree<MAXA, KS>(P, tree, rng, h, policy + (size_t)tree * P.A, reward ? reward[tree] : 0.0f,
                                             value[tree], path_col(P, tree));
+    }
+    if (P.S > 0 && hidden) {
+        const int t = valid ? tree : 0;
+        wave_copy_rows(hidden + (size_t)t * P.S, P.hidden + ((size_t)t * P.N + leaf) * P.hs, valid, P.S, P.tpw);
+    }
+    if (FUSE_SELECT) {
+        // the leaf rows just written by other lanes of this wave may be the next parent rows
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        select_phase<MAXA, KS>(P, tree, valid, rng, h, pbc_lds, parent_hidden, last_action, branch, mlp_input);
+    }
+    if (valid) {
+        P.rng_pos[tree] = rng.pack();
+        rng.save(P, tree);
+        P.hdr[tree] = h;
+    }
+}
+// The same kernel with the multi-player backup (smz_set_players: value_sum gains -value at the nodes of the root's opponents).
+// A kernel of its own, so that k_expand_backup keeps its instruction stream.
+template <int MAXA, int KS, bool FUSE_SELECT, bool AEX, bool PHX = false>
+__global__ void __launch_bounds__(kWave, MAXA > 16 ? 1 : SMZ_EB_WAVES) k_expand_backup_mp(Params Pin, const float *hidden, const float *reward,
+                                                            const float *policy, const float *value,
+                                                            float *parent_hidden, int32_t *last_action, uint8_t *branch,
+                                                            float *mlp_input) {
+    Params P = Pin;
+    P.tree0 = 0;
+    if (AEX) P.A = MAXA;
+    if (AEX) P.philox = PHX ? 1 : 0;          // (a constant in everything inlined below)
+    if (KS > 0) P.K = KS;
+    fix_layout(P, AEX, KS > 0);
+    uint32_t *rng_tile = rng_tile_ptr(P);
+    const bool narrow = rng_tile && P.tpw >= 16 && !P.philox;          // (wave-uniform) 16+ trees per wavefront: wave_stage_rng_narrow
+    const int n_staged = rng_tile ? (narrow ? kRngStageNarrow : kRngStage) : 0;
+    const int tree = blockIdx.x * P.tpw + threadIdx.x;
+    const bool valid = (int)threadIdx.x < P.tpw && tree < P.B && tree_active(P, tree);
+    const double *pbc_lds = stage_pbc(P);
+    const int packed = narrow ? wave_stage_rng_narrow(P, tree, valid, rng_tile) : wave_stage_rng<!AEX || PHX>(P, tree, valid, rng_tile);
+    RngT<!AEX || PHX> rng;
+    rng.bind(P, tree, valid);
+    TreeHdr h = {0, 0, 0.f, 0.f, 0, 0.f, 0, 0};
+    int leaf = 0;
+    if (valid) {
+        rng.load(P.mt + (size_t)tree * kMtN, packed, rng_tile + threadIdx.x * kRngStride, n_staged);
+        h = P.hdr[tree];
+        leaf = expand_backup_tree<MAXA, KS, false, false, false, true>(P, tree, rng, h, policy + (size_t)tree * P.A,
+                                                                     reward ? reward[tree] : 0.0f, value[tree], path_col(P, tree));
     }
     if (P.S > 0 && hidden) {
         const int t = valid ? tree : 0;
@@ -1549,6 +1595,7 @@ struct smz_handle {
     bool has_backup;
     std::vector<void *> allocs;
     char last_kernel[96];      // the single-launch search instantiation launched last, as rocprofv3 prints it (smz_last_kernel)
+    uint32_t *d_player_neg;    // [SMZ_MAX_PLAYER_CYCLE] sign masks of smz_set_players (allocated by its first multi-player call)
 };
 
 // the last-error text is shared by the translation units this file is compiled into (SMZ_PART)
@@ -1698,6 +1745,7 @@ int smz_create(const smz_config *cfg, smz_handle **out) {
     h->maxa = A <= 2 ? 2 : A <= 4 ? 4 : A <= 8 ? 8 : A <= 16 ? 16 : 32;
     h->root_ready = h->selected = false;
     h->pow_valid = false;
+    h->d_player_neg = nullptr;
     h->pow_T = 0.0;
     h->stats_on = false;
 
@@ -1921,9 +1969,15 @@ int smz_expand_backup(smz_handle *h, const float *hidden_dev, const float *rewar
     if (!h || !policy_dev || !value_dev) return fail(SMZ_ERR_INVALID, "smz_expand_backup: null argument%s");
     if (!h->selected) return fail(SMZ_ERR_STATE, "smz_expand_backup without a preceding smz_select%s");
     DeviceGuard guard(h->cfg.device);
-    SMZ_DISPATCH2_AEX(h->maxa, h->K, h->P.A == h->maxa && !h->P.philox, hipLaunchKernelGGL((k_expand_backup<MA, KS, false, AEX>), wave_grid(h->P), dim3(kWave), tree_lds_bytes(h->P),
-                                             (hipStream_t)stream, h->P, hidden_dev, reward_dev, policy_dev, value_dev,
-                                             (float *)nullptr, (int32_t *)nullptr, (uint8_t *)nullptr, (float *)nullptr));
+    if (h->P.n_cycle > 1) {     // multi-player handle (smz_set_players)
+        SMZ_DISPATCH2_AEX(h->maxa, h->K, h->P.A == h->maxa && !h->P.philox, hipLaunchKernelGGL((k_expand_backup_mp<MA, KS, false, AEX>), wave_grid(h->P), dim3(kWave), tree_lds_bytes(h->P),
+                                                 (hipStream_t)stream, h->P, hidden_dev, reward_dev, policy_dev, value_dev,
+                                                 (float *)nullptr, (int32_t *)nullptr, (uint8_t *)nullptr, (float *)nullptr));
+    } else {
+        SMZ_DISPATCH2_AEX(h->maxa, h->K, h->P.A == h->maxa && !h->P.philox, hipLaunchKernelGGL((k_expand_backup<MA, KS, false, AEX>), wave_grid(h->P), dim3(kWave), tree_lds_bytes(h->P),
+                                                 (hipStream_t)stream, h->P, hidden_dev, reward_dev, policy_dev, value_dev,
+                                                 (float *)nullptr, (int32_t *)nullptr, (uint8_t *)nullptr, (float *)nullptr));
+    }
     h->selected = false;
     return launch_check();
 }
@@ -1937,19 +1991,31 @@ int smz_expand_backup_select(smz_handle *h, const float *hidden_dev, const float
     if (!h || !policy_dev || !value_dev) return fail(SMZ_ERR_INVALID, "smz_expand_backup_select: null argument%s");
     if (!h->selected) return fail(SMZ_ERR_STATE, "smz_expand_backup_select without a preceding smz_select%s");
     DeviceGuard guard(h->cfg.device);
+    const bool mp = h->P.n_cycle > 1;      // multi-player handle (smz_set_players)
     if (h->P.philox && h->P.A == h->maxa && h->maxa <= 4) {       // Philox handles, exact action count: the specialised kernel too
-#define SMZ_EBS_PHX(MA, KS)                                                                                                  \
-        hipLaunchKernelGGL((k_expand_backup<MA, KS, true, true, true>), wave_grid(h->P), dim3(kWave), tree_lds_bytes(h->P),   \
+#define SMZ_EBS_PHX(KERNEL, MA, KS)                                                                                          \
+        hipLaunchKernelGGL((KERNEL<MA, KS, true, true, true>), wave_grid(h->P), dim3(kWave), tree_lds_bytes(h->P),           \
                            (hipStream_t)stream, h->P, hidden_dev, reward_dev, policy_dev, value_dev, parent_hidden_dev,     \
                            last_action_dev, branch_dev, mlp_input_dev)
-        if (h->maxa == 2) { if (h->K == 2) SMZ_EBS_PHX(2, 2); else SMZ_EBS_PHX(2, 0); }
-        else { if (h->K == 2) SMZ_EBS_PHX(4, 2); else SMZ_EBS_PHX(4, 0); }
+        if (mp) {
+            if (h->maxa == 2) { if (h->K == 2) SMZ_EBS_PHX(k_expand_backup_mp, 2, 2); else SMZ_EBS_PHX(k_expand_backup_mp, 2, 0); }
+            else { if (h->K == 2) SMZ_EBS_PHX(k_expand_backup_mp, 4, 2); else SMZ_EBS_PHX(k_expand_backup_mp, 4, 0); }
+        } else {
+            if (h->maxa == 2) { if (h->K == 2) SMZ_EBS_PHX(k_expand_backup, 2, 2); else SMZ_EBS_PHX(k_expand_backup, 2, 0); }
+            else { if (h->K == 2) SMZ_EBS_PHX(k_expand_backup, 4, 2); else SMZ_EBS_PHX(k_expand_backup, 4, 0); }
+        }
 #undef SMZ_EBS_PHX
         return launch_check();
     }
-    SMZ_DISPATCH2_AEX(h->maxa, h->K, h->P.A == h->maxa && !h->P.philox, hipLaunchKernelGGL((k_expand_backup<MA, KS, true, AEX>), wave_grid(h->P), dim3(kWave), tree_lds_bytes(h->P),
-                                             (hipStream_t)stream, h->P, hidden_dev, reward_dev, policy_dev, value_dev,
-                                             parent_hidden_dev, last_action_dev, branch_dev, mlp_input_dev));
+    if (mp) {
+        SMZ_DISPATCH2_AEX(h->maxa, h->K, h->P.A == h->maxa && !h->P.philox, hipLaunchKernelGGL((k_expand_backup_mp<MA, KS, true, AEX>), wave_grid(h->P), dim3(kWave), tree_lds_bytes(h->P),
+                                                 (hipStream_t)stream, h->P, hidden_dev, reward_dev, policy_dev, value_dev,
+                                                 parent_hidden_dev, last_action_dev, branch_dev, mlp_input_dev));
+    } else {
+        SMZ_DISPATCH2_AEX(h->maxa, h->K, h->P.A == h->maxa && !h->P.philox, hipLaunchKernelGGL((k_expand_backup<MA, KS, true, AEX>), wave_grid(h->P), dim3(kWave), tree_lds_bytes(h->P),
+                                                 (hipStream_t)stream, h->P, hidden_dev, reward_dev, policy_dev, value_dev,
+                                                 parent_hidden_dev, last_action_dev, branch_dev, mlp_input_dev));
+    }
     return launch_check();
 }
 #endif
@@ -2183,6 +2249,7 @@ extern "C" {
 #if SMZ_PART != 4 && SMZ_PART != 6
 int smz_search_mlp(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, int train,
                    smz_stream stream) {
+    if (h && h->P.n_cycle > 1) return fail(SMZ_ERR_INVALID, "smz_search_mlp: multi-player handles search step-wise only%s");
     return smz_internal_search_launch_narrow(h, desc, weights_dev, obs_dev, train,
                                              SearchActArgs{0.0, nullptr, nullptr, nullptr, nullptr, EnvStep{}}, nullptr, stream);
 }
@@ -2191,6 +2258,7 @@ int smz_search_mlp_act(smz_handle *h, const smz_mlp_desc *desc, const float *wei
                        double temperature, const double *pow_table_host, int32_t *action_dev, double *policy_dev,
                        double *child_visits_dev, float *root_value_dev, smz_stream stream) {
     if (!action_dev || !policy_dev || !child_visits_dev) return fail(SMZ_ERR_INVALID, "smz_search_mlp_act: null output%s");
+    if (h && h->P.n_cycle > 1) return fail(SMZ_ERR_INVALID, "smz_search_mlp_act: multi-player handles search step-wise only%s");
     return smz_internal_search_launch_narrow(h, desc, weights_dev, obs_dev, train,
                                              SearchActArgs{temperature, action_dev, policy_dev, child_visits_dev, root_value_dev,
                                                            EnvStep{}},
@@ -2205,6 +2273,8 @@ int smz_search_mlp_act_cartpole(smz_handle *h, const smz_mlp_desc *desc, const f
         return fail(SMZ_ERR_INVALID, "smz_search_mlp_act_cartpole: null argument%s");
     if (!h || !desc || h->P.A != 2 || desc->obs != 4)
         return fail(SMZ_ERR_INVALID, "smz_search_mlp_act_cartpole: the built-in env has 4 observations and 2 actions%s");
+    if (h->P.n_cycle > 1)
+        return fail(SMZ_ERR_INVALID, "smz_search_mlp_act_cartpole: multi-player handles search step-wise only%s");
     const smz_episode_ctl *c = env->ctl;
     if (c && (!c->step_count_dev || c->on_end < 0 || c->on_end > 2 || (c->on_end == 2 && !c->episode_dev) ||
               (c->on_end == 1 && !c->active_dev)))
@@ -2381,6 +2451,36 @@ int smz_synthetic_obs(float *obs_dev, int B, int obs_dim, uint64_t seed, int64_t
 int smz_set_active(smz_handle *h, const uint8_t *active_dev) {
     if (!h) return fail(SMZ_ERR_INVALID, "smz_set_active: null handle%s");
     h->P.active = active_dev;
+    return SMZ_OK;
+}
+
+int smz_set_players(smz_handle *h, int n_cycle, const float *cycle_values_host, const int32_t *root_player_dev) {
+    if (!h) return fail(SMZ_ERR_INVALID, "smz_set_players: null handle%s");
+    if (n_cycle < 1 || n_cycle > SMZ_MAX_PLAYER_CYCLE)
+        return fail(SMZ_ERR_INVALID, "smz_set_players: the turn cycle must have 1 .. SMZ_MAX_PLAYER_CYCLE (32) entries%s");
+    if (n_cycle > 1 && !cycle_values_host) return fail(SMZ_ERR_INVALID, "smz_set_players: null cycle_values_host%s");
+    if (n_cycle == 1) {          // one player: every backed-up value keeps its sign -- the plain kernels
+        h->P.n_cycle = 1;
+        h->P.root_player = nullptr;
+        return SMZ_OK;
+    }
+    uint32_t neg[SMZ_MAX_PLAYER_CYCLE] = {0u};
+    for (int r = 0; r < n_cycle; r++)
+        for (int j = 0; j < n_cycle; j++)
+            if (!(cycle_values_host[r] == cycle_values_host[(r + j) % n_cycle])) neg[r] |= 1u << j;
+    DeviceGuard guard(h->cfg.device);
+    if (!h->d_player_neg) {
+        void *p = nullptr;
+        HIP_TRY(hipMalloc(&p, SMZ_MAX_PLAYER_CYCLE * sizeof(uint32_t)));
+        h->allocs.push_back(p);
+        h->d_player_neg = (uint32_t *)p;
+    }
+    // (synchronous: kernels already enqueued on any stream have read the previous table)
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(h->d_player_neg, neg, sizeof(neg), hipMemcpyHostToDevice));
+    h->P.player_neg = h->d_player_neg;
+    h->P.n_cycle = n_cycle;
+    h->P.root_player = root_player_dev;
     return SMZ_OK;
 }
 

@@ -632,6 +632,7 @@ __global__ void __launch_bounds__(kVW *kWave) SMZ_VISION_OCC k_search_vision(Par
 int search_vision_launch(smz_handle *h, const smz_vision_desc *desc, const float *weights_dev, const float *hidden0_dev,
                          const float *policy0_dev, int train, ActOut act, const double *pow_table_host, smz_stream stream) {
     if (!h || !desc || !weights_dev || !hidden0_dev || !policy0_dev) return fail(SMZ_ERR_INVALID, "smz_search_vision: null argument%s");
+    if (h->P.n_cycle > 1) return fail(SMZ_ERR_INVALID, "smz_search_vision: multi-player handles search step-wise only%s");
     smz_vision_desc t = *desc;
     if (smz_vision_layout(&t) != SMZ_OK || t.total_floats != desc->total_floats)
         return fail(SMZ_ERR_INVALID, "smz_search_vision: descriptor does not describe a vision_model weight buffer%s");

@@ -93,6 +93,35 @@ class SearchEngine:
         self._active = active
         _lib.check(self.lib.smz_set_active(self.h, _ptr(active)))
 
+    def set_players(self, cycle_values, root_player=None):
+        """Multi-player search (smz_set_players): `cycle_values` are the turn cycle's player values (Player_cycle.cycle_map,
+        at most 32); more than one selects the multi-player backup of the step-wise kernels -- value_sum gains -value at
+        every node whose player's value differs from the root's (mcts:299-308).  The root player of every tree is read from
+        `self.root_player` (int32 [B], engine-owned, so a captured graph stays valid while set_root_player rewrites it)."""
+        vals = np.ascontiguousarray(cycle_values, dtype=np.float32).reshape(-1)
+        if len(vals) > 1 and getattr(self, "root_player", None) is None:
+            self.root_player = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.smz_set_players(self.h, len(vals), vals.ctypes.data_as(C.c_void_p),
+                                            _ptr(self.root_player) if len(vals) > 1 else None))
+        self.n_cycle = len(vals)
+        if root_player is not None:
+            self.set_root_player(root_player)
+
+    def set_root_player(self, to_play):
+        """Root player index per tree (an int, a host array or a device tensor of B entries), copied into `self.root_player`
+        on the current stream."""
+        if getattr(self, "n_cycle", 1) <= 1:
+            raise RuntimeError("set_root_player needs a multi-player engine (set_players with more than one player)")
+        if torch.is_tensor(to_play):
+            src = to_play.reshape(-1).to(device=self.device, dtype=torch.int32)
+        elif np.isscalar(to_play):
+            self.root_player.fill_(int(to_play))
+            return
+        else:
+            src = torch.from_numpy(np.ascontiguousarray(to_play, dtype=np.int32).reshape(-1))
+        assert src.numel() == self.B, (src.numel(), self.B)
+        self.root_player.copy_(src)
+
     def enable_leaf_ids(self, on=True):
         """smz_set_leaf_ids_out: every selection also writes (leaf node id, parent node id) per tree to `self.leaf_ids`
         [B,2] int32, so that a network kernel can take and put its rows in the tree's own hidden-state storage

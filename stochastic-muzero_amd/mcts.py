@@ -18,8 +18,8 @@ from .engine import SearchEngine
 
 
 class Player_cycle:
-    """Turn order bookkeeping of mcts:38-72, single-player form (every config of the reference uses 1 player; the
-    backup sign is then always + , mcts:302-305)."""
+    """Turn order bookkeeping of mcts:38-72: `cycle_map` holds the players' values in turn order (range(number_of_player),
+    or the numbers of a custom loop "1>2>1>3"); `global_step()` is the root player index of the next search."""
 
     def __init__(self, number_of_player=None, custom_loop=None):
         if custom_loop is not None and isinstance(custom_loop, str):
@@ -42,6 +42,37 @@ class Player_cycle:
     def proximate_player_step(self, player_index):
         return (player_index + 1) % len(self.cycle_map)
 
+    def player_in_play(self, player_index):
+        return self.cycle_map[player_index % len(self.cycle_map)]
+
+
+def cycle_values(number_of_player, custom_loop):
+    """The turn cycle's player values as float32 (Player_cycle.cycle_map; the reference compares them as tensors)."""
+    return np.asarray(Player_cycle(number_of_player, custom_loop).cycle_map, np.float32)
+
+
+def player_sign_masks(values):
+    """uint32 [L]: bit j of entry r is set iff the player j turns after root player r has another value -- the nodes whose
+    value_sum gains -value in the backup (mcts:299-308).  What smz_set_players computes on the host."""
+    v = np.asarray(values, np.float32)
+    L = len(v)
+    out = np.zeros(L, np.uint32)
+    for r in range(L):
+        for j in range(L):
+            if not v[r] == v[(r + j) % L]:
+                out[r] |= np.uint32(1 << j)
+    return out
+
+
+def to_play_at_depth(root_to_play, depth, n_cycle):
+    """Player index of a node at `depth` below a root playing `root_to_play`: the root's children move on one player, and
+    below them only the children of chance nodes do (mcts:207, 296) -- 2 (d >> 2) + ((d & 3) != 0) turns in all."""
+    d = np.asarray(depth, np.int64)
+    return (np.asarray(root_to_play, np.int64) + 2 * (d >> 2) + ((d & 3) != 0)) % int(n_cycle)
+
+
+MAX_PLAYER_CYCLE = 32      # SMZ_MAX_PLAYER_CYCLE: bits of a sign mask
+
 
 def _validate(pb_c_base, pb_c_init, discount, root_dirichlet_alpha, root_exploration_fraction, num_simulations,
               maxium_action_sample, number_of_player, custom_loop):
@@ -55,9 +86,9 @@ def _validate(pb_c_base, pb_c_init, discount, root_dirichlet_alpha, root_explora
     assert isinstance(num_simulations, int) and num_simulations >= 0, "num_simulations ∈ int | {0 < num_simulations < +inf)"
     assert isinstance(number_of_player, int) and number_of_player >= 1, "number_of_player ∈ int | {1 < number_of_player < +inf)"
     assert isinstance(custom_loop, str) or custom_loop is None, "custom_loop ∈ str | 1>2>3>3 "
-    if number_of_player != 1 or custom_loop is not None:
-        raise NotImplementedError("the GPU engine implements the single-player backup (number_of_player=1), the only "
-                                  "setting any reference config uses")
+    n = len(Player_cycle(number_of_player, custom_loop).cycle_map)
+    if n > MAX_PLAYER_CYCLE:
+        raise ValueError(f"the turn cycle has {n} entries; the engine supports at most {MAX_PLAYER_CYCLE}")
 
 
 class _Hyper:
@@ -70,6 +101,14 @@ class _Hyper:
         self.num_simulations, self.maxium_action_sample = num_simulations, maxium_action_sample
         self.number_of_player, self.custom_loop = number_of_player, custom_loop
         self.cycle = Player_cycle(number_of_player=number_of_player, custom_loop=custom_loop)
+        # more than one entry in the turn cycle: the multi-player backup (step-wise kernels only)
+        self.cycle_values = cycle_values(number_of_player, custom_loop)
+        self.n_cycle = len(self.cycle_values)
+
+    def _bind_players(self, eng):
+        """Hands the turn cycle to a new engine (SearchEngine.set_players)."""
+        if self.n_cycle > 1:
+            eng.set_players(self.cycle_values)
 
     def _engine_kwargs(self):
         return dict(num_simulations=self.num_simulations, maxium_action_sample=self.maxium_action_sample,
@@ -107,6 +146,7 @@ class BatchedMCTS(_Hyper):
         self.rng_mode = resolve_rng_mode(rng_mode, self.num_trees)
         self.use_graph, self.fused, self.single_launch = bool(use_graph), bool(fused), bool(single_launch)
         self.engine = None
+        self._to_play = None
         self._graph = None
         self._graph_key = None
         self._graph_heads = None
@@ -124,6 +164,7 @@ class BatchedMCTS(_Hyper):
                                        rng_mode=self.rng_mode, **self._engine_kwargs())
             if getattr(self, "_active", None) is not None:
                 self.engine.set_active(self._active)
+            self._bind_players(self.engine)
             self._graph = None
         return self.engine
 
@@ -151,6 +192,8 @@ class BatchedMCTS(_Hyper):
         if getattr(self, "_pending_seed", None) is not None:
             eng.seed(self._pending_seed)
             self._pending_seed = None
+        if not torch.cuda.is_current_stream_capturing():
+            self._stage_to_play(eng)                 # (a captured graph reads the buffer staged before its replay)
         eng.root_init(hidden, policy, train=train)
         if hasattr(heads, "bind_engine"):            # heads that may leave the rows in the tree (large batches)
             want = heads.bind_engine(eng)
@@ -192,21 +235,33 @@ class BatchedMCTS(_Hyper):
             self._search(self._static_obs, heads, train)
         self._graph, self._graph_key = g, key
 
-    def run(self, observations, heads, train=True, act_temperature=None, env_step=None, record_obs=None):
+    def run(self, observations, heads, train=True, act_temperature=None, env_step=None, record_obs=None, to_play=None):
         """observations: [B, ...] float32 tensor on the engine's device.  Returns the engine; the search has been
         enqueued on the current stream (read results with engine.root_stats() / engine.act()).
+        `to_play` (multi-player searches: number_of_player > 1 or a custom loop): int [B] root player index of every tree
+        (Player_cycle.global_step() of the reference: the move number in the current game, mod the cycle length), a host
+        array or a device tensor, copied into the engine's buffer on the current stream; None = 0 for every tree.  These
+        searches run on the step-wise kernels.
         With HipMlpHeads the whole search is ONE kernel launch (smz_search_mlp) when it fits in LDS; otherwise the
         step-wise kernels run, captured in a HIP graph unless use_graph is off.
         `env_step` (envs.CartPoleVec.fused_step): the single launch also steps the built-in env and appends the record;
         `engine.env_stepped` says whether it did (any other path leaves the env to the caller).
         `record_obs` (a float32 tensor the size of `observations`): the representation launch of the vision family copies the
         frames it reads there (smz_vision_initial_record); `engine.obs_recorded` says whether that happened."""
+        self._to_play = to_play
         eng = self._run(observations, heads, train, act_temperature, env_step, record_obs)
         eng.obs_recorded = record_obs is not None and self._recorded
         return eng
 
+    def _stage_to_play(self, eng):
+        if self.n_cycle > 1:
+            eng.set_root_player(0 if self._to_play is None else self._to_play)
+
     def _run(self, observations, heads, train, act_temperature, env_step, record_obs):
         self._recorded = False
+        if self.n_cycle > 1:
+            # the multi-player backup exists in the step-wise kernels only (the single launch refuses such a handle)
+            return self._run_stepwise(observations, heads, train)
         # (single_launch_max_trees: where the step-wise kernels overtake the single launch)
         if (self.single_launch and isinstance(getattr(heads, "desc", None), _lib.MlpDesc) and self._single is not False
                 and self.num_trees <= self.single_launch_max_trees):
@@ -246,6 +301,9 @@ class BatchedMCTS(_Hyper):
                 self._single = False
                 warnings.warn("single-launch vision search is outside its limits for this configuration "
                               f"({err}): using the step-wise kernels")
+        return self._run_stepwise(observations, heads, train)
+
+    def _run_stepwise(self, observations, heads, train):
         if not self.use_graph:
             self._search(observations, heads, train)
             return self.engine
@@ -257,6 +315,7 @@ class BatchedMCTS(_Hyper):
             self._build_graph(observations, heads, train, key)
             self._graph_heads = heads
         self._static_obs.copy_(observations)
+        self._stage_to_play(self.engine)          # the graph holds the buffer's address, not its contents
         self._graph.replay()
         return self.engine
 
@@ -271,8 +330,9 @@ class ChildView:
         return len(self.children) > 0
 
 
-def _build_views(dump, A, K, hidden_rows=None):
-    """Node objects (mcts:6-21) for one dumped tree; children dicts keyed by action in ascending order."""
+def _build_views(dump, A, K, hidden_rows=None, root_to_play=0, n_cycle=1):
+    """Node objects (mcts:6-21) for one dumped tree; children dicts keyed by action in ascending order.  `to_play` is the
+    player index the reference's nodes carry (mcts:186-207, 296) for a root playing `root_to_play` of `n_cycle`."""
     n = dump["n_nodes"]
     nodes = []
     for i in range(n):
@@ -295,8 +355,10 @@ def _build_views(dump, A, K, hidden_rows=None):
                 c = cb + j
                 depth[c] = depth[i] + 1
                 nodes[i].children[np.int64(dump["action"][c])] = nodes[c]
+    to_play = to_play_at_depth(root_to_play, depth, n_cycle)
     for i in range(n):
         nodes[i].is_chance = bool((depth[i] >> 1) & 1)
+        nodes[i].to_play = int(to_play[i])
     for a in range(A):
         nodes[1 + a].prior = np.float64(dump["root_priors"][a])
     nodes[0].prior = 0
@@ -333,13 +395,16 @@ class Monte_carlo_tree_search(_Hyper):
         (game.py:213 continues from there)."""
         self.model = model
         h0 = model.representation_function_inference(observation)
-        self.cycle.global_step()
+        to_play = self.cycle.global_step()            # the root's player (mcts:186-194)
         policy, _value = model.prediction_function_inference(h0)     # value discarded (mcts:319-321)
         h0_flat = torch.as_tensor(h0).detach().reshape(1, -1).float()
         A, S = int(np.asarray(policy).shape[-1]), int(h0_flat.shape[1])
         if self._engine is None or (self._engine.A, self._engine.S) != (A, S):
             self._engine = SearchEngine(1, A, S, **self._engine_kwargs())
+            self._bind_players(self._engine)
         eng = self._engine
+        if self.n_cycle > 1:
+            eng.set_root_player(to_play)
         if use_global_numpy_stream:
             _, key, pos, *_ = np.random.get_state()
             eng.set_rng_state(0, key, pos)
@@ -366,6 +431,6 @@ class Monte_carlo_tree_search(_Hyper):
         if use_global_numpy_stream:
             key, pos = eng.get_rng_state(0)
             np.random.set_state(("MT19937", key, pos, 0, 0.0))
-        self.root = _build_views(eng.dump_tree(0), A, eng.K)
+        self.root = _build_views(eng.dump_tree(0), A, eng.K, root_to_play=to_play, n_cycle=self.n_cycle)
         self.root.hidden_state = h0
         return self.root

@@ -420,6 +420,13 @@ def _search_phase(env, heads, mcts, chunk, t, temperature, train=True):
     owed = getattr(chunk, "owed_obs", None)
     if owed is not None and owed[1] is env.obs and getattr(heads, "records_frames", False):
         kw["record_obs"] = chunk.obs[owed[0]]
+    if getattr(mcts, "n_cycle", 1) > 1:
+        # multi-player: the root player of env e's search is its move number in the current game (the reference's
+        # Player_cycle.global_step, reset at every game end, self_play.py:58, 96), taken mod the cycle length by the kernel
+        try:
+            kw["to_play"] = env.step_count
+        except AttributeError as err:
+            raise RuntimeError(f"a multi-player search needs the env's move counter (env.step_count): {err}") from None
     eng = mcts.run(env.obs, heads, train=train, act_temperature=temperature, **kw)
     if owed is not None:
         if getattr(eng, "obs_recorded", False):
@@ -546,7 +553,7 @@ def reanalyse_games(games, model, mcts, device, train=False):
     for lo in range(0, len(obs), B):
         rows = obs[lo:lo + B]
         batch = torch.stack(rows + [rows[-1]] * (B - len(rows))).to(device=device, dtype=torch.float32).contiguous()
-        eng = mcts.run(batch, heads, train=train)
+        eng = mcts.run(batch, heads, train=train, **_to_play_kw(mcts, [t - 1 for _, t in index[lo:lo + B]], B))
         _, _, child_visits, root_value = eng.act(0.0)
         torch.cuda.synchronize(device)
         cv, rv = child_visits.cpu().numpy(), root_value.cpu().numpy()
@@ -556,6 +563,16 @@ def reanalyse_games(games, model, mcts, device, train=False):
             games[gi].reanalyzed = True
         done += len(rows)
     return done
+
+
+def _to_play_kw(mcts, positions, B):
+    """Multi-player searches: the root player of a stored position is its index in the game (the reference's
+    Player_cycle.global_step, reset at every game end); the padding trees repeat the last one."""
+    if getattr(mcts, "n_cycle", 1) <= 1:
+        return {}
+    pos = np.asarray(positions, np.int64)
+    pos = np.concatenate([pos, np.repeat(pos[-1:], B - len(pos))]) if len(pos) < B else pos
+    return dict(to_play=(pos % mcts.n_cycle).astype(np.int32))
 
 
 def reanalyse_replay_games(games, model, mcts, device, temperature=0.0, train=True):
@@ -579,7 +596,8 @@ def reanalyse_replay_games(games, model, mcts, device, temperature=0.0, train=Tr
     for lo in range(0, len(obs), B):
         rows = obs[lo:lo + B]
         batch = torch.stack(rows + [rows[-1]] * (B - len(rows))).to(device=device, dtype=torch.float32).contiguous()
-        eng = mcts.run(batch, heads, train=train, act_temperature=temperature)
+        eng = mcts.run(batch, heads, train=train, act_temperature=temperature,
+                       **_to_play_kw(mcts, [i for _, i in index[lo:lo + B]], B))
         action, policy, child_visits, root_value = eng.act(temperature)
         torch.cuda.synchronize(device)
         a, p, cv, rv = (t.cpu().numpy() for t in (action, policy, child_visits, root_value))
@@ -642,7 +660,8 @@ def reanalyse_replay_records(games, model, mcts, device, temperature=0.0, train=
     for lo in range(0, P, B):
         part = obs[lo:lo + B]
         batch = torch.from_numpy(np.concatenate([part, np.repeat(part[-1:], B - len(part), 0)]) if len(part) < B else part)
-        eng = mcts.run(batch.to(device).contiguous(), heads, train=train, act_temperature=temperature)
+        eng = mcts.run(batch.to(device).contiguous(), heads, train=train, act_temperature=temperature,
+                       **_to_play_kw(mcts, step[lo:lo + B], B))
         action, policy, child_visits, root_value = eng.act(temperature)
         torch.cuda.synchronize(device)
         m = len(part)

@@ -258,6 +258,46 @@ int smz_mlp_recurrent(const smz_mlp_desc *desc, const float *weights_dev, const 
                       const uint8_t *branch_dev, float *hidden_out_dev, float *reward_out_dev, float *policy_out_dev,
                       float *value_out_dev, int B, smz_stream stream);
 
+/* ---- fused heads of the `lstm_model` family (neural_network_lstm_model.py) ---------------------------------------- */
+/* Replaces the same five *_inference calls as the smz_mlp_* entry points, for heads built as
+ * Sequential(Linear(in, H), LSTM(H, O, num_layers = L), extract_tensor).  The reference calls each head with batch 1, i.e.
+ * as a length-1 sequence from h0 = c0 = 0, so per LSTM layer (PyTorch gate order i, f, g, o)
+ *     gates = W_ih x + b_ih + b_hh,   c = sigmoid(i) * tanh(g),   h = sigmoid(o) * tanh(c)
+ * (W_hh multiplies h0 = 0 and f multiplies c0 = 0: neither is stored).  Every row of a batch is such a sequence of its own.
+ * Layer 0 has no activation before it, so its input Linear is folded in on the host: W = W_ih0[i,g,o] * W_lin,
+ * b = W_ih0[i,g,o] * b_lin + b_ih0 + b_hh0 (float64 products rounded once to float32).
+ *
+ * Trunks (index t): 0 dynamics reward (S+A -> S support logits), 1 dynamics next state (S+A -> S, scaled),
+ * 2 afterstate dynamics next state (S+A -> S, scaled), 3 prediction policy (S -> A logits), 4 prediction value (S -> S),
+ * 5 afterstate prediction policy, 6 afterstate prediction value.
+ * Packed weight buffer: float32, every piece starting at a multiple of 4 floats.  Layer l of trunk t is a K x 3O matrix
+ * (K = the trunk's input width for l = 0, O for l >= 1; columns [0,O) gate i, [O,2O) gate g, [2O,3O) gate o) stored
+ * input-major and 4-way interleaved as in smz_mlp_desc but with row width 3O: element (k, c) -> base + ((k / 4) * 3O + c) * 4
+ * + k % 4, K zero-padded to a multiple of 4; its bias is 3O floats.  Matrix at off[2 * (t * SMZ_LSTM_MAX_LAYERS + l)], bias
+ * at the next index.  The representation Linear(obs, S) (same layout, row width S) sits at off[SMZ_LSTM_REP] (bias at
+ * SMZ_LSTM_REP + 1), after the trunks.  Each of the two regions ends with SMZ_LSTM_SLACK zero floats. */
+enum { SMZ_LSTM_TRUNKS = 7, SMZ_LSTM_MAX_LAYERS = 4, SMZ_LSTM_REP = 2 * SMZ_LSTM_TRUNKS * SMZ_LSTM_MAX_LAYERS,
+       SMZ_LSTM_OFFSETS = SMZ_LSTM_REP + 2, SMZ_LSTM_SLACK = 256 };
+typedef struct {
+    int32_t obs, A, S, L;      /* observation width, actions, state_space_dimensions, number_of_hidden_layer (1..4) */
+    int32_t total_floats;      /* size of the packed buffer */
+    int32_t recurrent_floats;  /* [0, recurrent_floats): the seven trunks (staged in LDS by smz_lstm_recurrent) */
+    int32_t lds_bytes;         /* dynamic LDS of one smz_lstm_recurrent workgroup */
+    int32_t off[SMZ_LSTM_OFFSETS];
+} smz_lstm_desc;
+/* Fills total_floats, recurrent_floats, lds_bytes and off[] from obs/A/S/L.  SMZ_ERR_INVALID when S or A exceed 64 (one
+ * LSTM unit per lane), L is outside 1..4, or the trunks do not fit a CU's 160 KB of LDS (use the torch heads then). */
+int smz_lstm_layout(smz_lstm_desc *desc);
+/* representation + root prediction: obs_dev [B,obs] -> hidden_out_dev [B,S] (scaled), policy_out_dev [B,A] (softmax) */
+int smz_lstm_initial(const smz_lstm_desc *desc, const float *weights_dev, const float *obs_dev, float *hidden_out_dev,
+                     float *policy_out_dev, int B, smz_stream stream);
+/* recurrent step for all trees: mlp_input_dev [B,S+A] (state | one-hot action, as smz_select writes it) and branch_dev [B]
+ * -> hidden_out_dev [B,S], reward_out_dev [B] (0 on the afterstate branch; may be NULL), policy_out_dev [B,A],
+ * value_out_dev [B].  Each row evaluates only the pair of networks its branch selects. */
+int smz_lstm_recurrent(const smz_lstm_desc *desc, const float *weights_dev, const float *mlp_input_dev,
+                       const uint8_t *branch_dev, float *hidden_out_dev, float *reward_out_dev, float *policy_out_dev,
+                       float *value_out_dev, int B, smz_stream stream);
+
 /* ---- fused heads of the `vision_model` family (neural_network_vision_model.py:41-515) ---------------------------- */
 /* Replaces, for the reference's ResNet-v2 family on 98x98x3 frames (hidden state 3x7x7 = 147 floats, channel major),
  * the same five *_inference calls (muzero_model.py:802-909) as the smz_mlp_* entry points do for `mlp_model`.

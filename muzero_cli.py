@@ -134,13 +134,8 @@ def main(argv):
         if mz.get("load"):
             model = model_mod.Muzero.from_checkpoint(opts["checkpoint_dir"], tag=lc["model_tag_number"])
         else:
-            assert mz["model_structure"] == "mlp_model", "fresh models are built for mlp_model"
             probe = make_env(config["game"]["env"], 1, device, 0)
-            model = model_mod.Muzero(model_structure="mlp_model", observation_space_dimensions=probe.obs_dim,
-                                     action_space_dimensions=probe.num_actions,
-                                     state_space_dimensions=mz["state_space_dimensions"],
-                                     hidden_layer_dimensions=mz["hidden_layer_dimensions"],
-                                     number_of_hidden_layer=mz["number_of_hidden_layer"], random_tag=lc["model_tag_number"])
+            model = fresh_model(mz, probe.obs_dim, probe.num_actions, lc["model_tag_number"])
         search = mcts_mod.BatchedMCTS(n_env, **mcts_kwargs(config))
         search.seed(np.arange(n_env, dtype=np.uint64) + np.uint64(config["random_seed"]["np_random_seed"]))
         limit = int(config["gameplay"]["limit_of_game_play"])
@@ -162,6 +157,18 @@ def main(argv):
             model_directory=opts["checkpoint_dir"])
         out["train"] = dict(iterations=iters, games=len(buffer), rewards=reward[1:])
     return out
+
+
+def fresh_model(mz, obs_dim, num_actions, tag):
+    """A new model from the config's "muzero" section (the reference's Muzero(**config["muzero"]) for vector games)."""
+    from importlib import import_module
+    import stochastic_muzero_amd  # noqa: F401
+    model_mod = import_module("stochastic-muzero_amd.model")
+    assert mz["model_structure"] in ("mlp_model", "lstm_model"), "fresh models are built for mlp_model and lstm_model"
+    return model_mod.Muzero(model_structure=mz["model_structure"], observation_space_dimensions=obs_dim,
+                            action_space_dimensions=num_actions, state_space_dimensions=mz["state_space_dimensions"],
+                            hidden_layer_dimensions=mz["hidden_layer_dimensions"],
+                            number_of_hidden_layer=mz["number_of_hidden_layer"], random_tag=tag)
 
 
 if __name__ == "__main__":

@@ -34,6 +34,14 @@ class MlpDesc(C.Structure):
                 ("OP", C.c_int32), ("total_floats", C.c_int32), ("off", C.c_int32 * 30)]
 
 
+class LstmDesc(C.Structure):
+    """smz_lstm_desc (include/smz.h): dimensions + float offsets of the packed lstm_model weight buffer."""
+    TRUNKS, MAX_LAYERS = 7, 4
+    REP = 2 * TRUNKS * MAX_LAYERS
+    _fields_ = [("obs", C.c_int32), ("A", C.c_int32), ("S", C.c_int32), ("L", C.c_int32), ("total_floats", C.c_int32),
+                ("recurrent_floats", C.c_int32), ("lds_bytes", C.c_int32), ("off", C.c_int32 * (REP + 2))]
+
+
 class VisionDesc(C.Structure):
     """smz_vision_desc (include/smz.h): dimensions + float offsets of the packed vision_model weight buffer."""
     _fields_ = [("A", C.c_int32), ("S", C.c_int32), ("H", C.c_int32), ("L", C.c_int32), ("OP", C.c_int32),
@@ -90,6 +98,9 @@ SIGNATURES = {
     "smz_mlp_recurrent": (C.c_int, [C.POINTER(MlpDesc), _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "smz_mlp_layout_wide": (C.c_int, [C.POINTER(MlpDesc)]),
     "smz_mlp_recurrent_wide": (C.c_int, [C.POINTER(MlpDesc), _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
+    "smz_lstm_layout": (C.c_int, [C.POINTER(LstmDesc)]),
+    "smz_lstm_initial": (C.c_int, [C.POINTER(LstmDesc), _P, _P, _P, _P, C.c_int, _P]),
+    "smz_lstm_recurrent": (C.c_int, [C.POINTER(LstmDesc), _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "smz_vision_layout": (C.c_int, [C.POINTER(VisionDesc)]),
     "smz_vision_initial": (C.c_int, [C.POINTER(VisionDesc), _P, _P, _P, _P, C.c_int, _P]),
     "smz_vision_initial_record": (C.c_int, [C.POINTER(VisionDesc), _P, _P, _P, _P, _P, C.c_int, _P]),

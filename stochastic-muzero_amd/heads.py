@@ -13,8 +13,9 @@ Two implementations of the same interface:
   FusedMlpHeads  -- `mlp_model` family (neural_network_mlp_model.py:5-250): the two dynamics trunks share their
                     input and the two prediction trunks share theirs, so each pair is evaluated as ONE stacked
                     linear layer + ONE block-structured output layer (4 GEMMs per round instead of 10).
-  ModuleHeads    -- any head family following the reference's module signatures (vision, lstm, ...): calls the
-                    five torch modules batched and uses the same epilogues.
+  ModuleHeads    -- any head family following the reference's module signatures whose modules treat the rows of a
+                    batch independently (vision, ...): calls the five torch modules batched and uses the same
+                    epilogues.  Not `lstm_model`: its modules read a 2-D batch as ONE sequence (LstmTorchHeads).
 Interface:
   initial(obs)                      -> hidden [B,S] f32, policy [B,A] f32 (softmaxed; the root value is unused, mcts:319)
   recurrent(mlp_input/hidden, last_action, branch) -> hidden' [B,S], reward [B], policy [B,A], value [B]
@@ -384,6 +385,178 @@ class HipVisionHeads:
         _lib.check(self.lib.smz_vision_recurrent(C.byref(self.desc), _ptr(self.weights), _ptr(ph), ph.stride(0),
                                                  _ptr(engine.last_action), _ptr(engine.branch), _ptr(hidden), _ptr(reward),
                                                  _ptr(policy), _ptr(value), B, _stream(self.device)))
+        return hidden, reward, policy, value
+
+
+def _lstm_trunk(seq):
+    """(Linear, nn.LSTM, extract_tensor) -> (W_lin [H,in], b_lin [H], [(W_ih [4O,K], b_ih, b_hh) per layer]), float32."""
+    lin, lstm = seq[0], seq[1]
+    if not isinstance(lin, torch.nn.Linear) or not isinstance(lstm, torch.nn.LSTM):
+        raise ValueError("not an lstm_model trunk (Linear, LSTM, extract_tensor)")
+    if not lstm.bias or lstm.bidirectional or getattr(lstm, "proj_size", 0) or lin.bias is None:
+        raise ValueError("lstm_model trunks are unidirectional LSTMs with biases and no projection")
+    t = lambda x: x.detach().float()
+    layers = [(t(getattr(lstm, f"weight_ih_l{l}")), t(getattr(lstm, f"bias_ih_l{l}")), t(getattr(lstm, f"bias_hh_l{l}")))
+              for l in range(lstm.num_layers)]
+    return t(lin.weight), t(lin.bias), layers
+
+
+def _unwrap(m):
+    return m.module if isinstance(m, torch.nn.DataParallel) else m
+
+
+def lstm_trunks_from_modules(representation, prediction, afterstate_prediction, afterstate_dynamics, dynamics):
+    """The seven recurrent trunks in smz_lstm_desc order + the representation Linear, from modules with the reference's
+    attributes (compat_lstm.py)."""
+    rep, pre, apr, ady, dyn = (_unwrap(m) for m in (representation, prediction, afterstate_prediction, afterstate_dynamics,
+                                                     dynamics))
+    trunks = [_lstm_trunk(s) for s in (dyn.reward, dyn.next_state_normalized, ady.next_state_normalized, pre.policy,
+                                       pre.value, apr.policy, apr.value)]
+    if len({len(t[2]) for t in trunks}) != 1:
+        raise ValueError("lstm_model trunks with different numbers of layers")
+    return trunks, (rep.state_norm.weight.detach().float(), rep.state_norm.bias.detach().float())
+
+
+class LstmTorchHeads:
+    """`lstm_model` heads (compat_lstm.py) on torch-ROCm ops + the HIP softmax / support-decode epilogues.
+
+    The reference calls every head with batch 1: one length-1 sequence from h0 = c0 = 0.  Here every tree is such a
+    sequence of its own (seq 1, batch B), which is what nn.LSTM computes for a [1, B, H] input: per layer
+    gates = W_ih x + b_ih + b_hh (W_hh multiplies h0 = 0), c = sigmoid(i) tanh(g) (f multiplies c0 = 0),
+    h = sigmoid(o) tanh(c).  The cell is written out with plain ops instead of calling the LSTM module so that the
+    step-wise search stays capturable in one graph (static shapes, no library RNN descriptors or workspaces).  Both
+    pairs of networks run for every tree and the branch flag selects, as in ModuleHeads."""
+    wants_mlp_input, wants_parent_hidden = True, False
+
+    def __init__(self, representation, prediction, afterstate_prediction, afterstate_dynamics, dynamics, num_actions,
+                 support_size, device):
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        trunks, rep = lstm_trunks_from_modules(representation, prediction, afterstate_prediction, afterstate_dynamics,
+                                               dynamics)
+        mv = lambda x: x.to(self.device).contiguous()
+        self.trunks = [(mv(w), mv(b), [(mv(wi), mv(bi), mv(bh)) for wi, bi, bh in layers]) for w, b, layers in trunks]
+        self.rep = (mv(rep[0]), mv(rep[1]))
+        self.A, self.S = int(num_actions), int(support_size)
+        self._buf = {}
+
+    def _out(self, name, shape, dtype=torch.float32):
+        t = self._buf.get(name)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = self._buf[name] = torch.empty(*shape, dtype=dtype, device=self.device)
+        return t
+
+    @staticmethod
+    def _scale(x):
+        lo = x.amin(dim=1, keepdim=True)
+        span = x.amax(dim=1, keepdim=True) - lo
+        return (x - lo) / torch.where(span < 1e-5, span + 1e-5, span)
+
+    def _trunk(self, t, x):
+        w, b, layers = self.trunks[t]
+        h = F.linear(x, w, b)
+        for wi, bi, bh in layers:
+            i, _, g, o = (F.linear(h, wi, bi) + bh).chunk(4, 1)
+            h = torch.sigmoid(o) * torch.tanh(torch.sigmoid(i) * torch.tanh(g))
+        return h
+
+    @torch.no_grad()
+    def initial(self, obs):
+        B = obs.shape[0]
+        hidden = self._scale(F.linear(obs, *self.rep)).contiguous()
+        logits = self._trunk(3, hidden).contiguous()
+        policy = self._out("p0", (B, self.A))
+        _lib.check(self.lib.smz_policy_softmax(_ptr(logits), self.A, _ptr(policy), B, _stream(self.device)))
+        return hidden, policy
+
+    @torch.no_grad()
+    def recurrent(self, engine):
+        x, branch = engine.mlp_input, engine.branch
+        B = x.shape[0]
+        m = branch.bool()
+        rl = self._trunk(0, x).contiguous()
+        hidden = torch.where(m[:, None], self._scale(self._trunk(1, x)), self._scale(self._trunk(2, x))).contiguous()
+        rdec = self._out("rdec", (B,))
+        _lib.check(self.lib.smz_support_decode(_ptr(rl), self.S, _ptr(rdec), B, _stream(self.device)))
+        reward = torch.where(m, rdec, torch.zeros_like(rdec)).contiguous()
+        pl = torch.where(m[:, None], self._trunk(3, hidden), self._trunk(5, hidden)).contiguous()
+        vl = torch.where(m[:, None], self._trunk(4, hidden), self._trunk(6, hidden)).contiguous()
+        policy, value = self._out("p", (B, self.A)), self._out("v", (B,))
+        _lib.check(self.lib.smz_policy_softmax(_ptr(pl), self.A, _ptr(policy), B, _stream(self.device)))
+        _lib.check(self.lib.smz_support_decode(_ptr(vl), self.S, _ptr(value), B, _stream(self.device)))
+        return hidden, reward, policy, value
+
+
+class HipLstmHeads:
+    """`lstm_model` heads evaluated by hand-written HIP kernels (smz_lstm_initial / smz_lstm_recurrent, csrc/smz_lstm.hip):
+    the seven recurrent trunks packed once into the LDS layout of smz_lstm_desc (include/smz.h), each trunk's input Linear
+    folded into its first LSTM layer on the host (float64 products, rounded once), forget gates and W_hh dropped (zero
+    state).  Raises ValueError when the trunks do not fit a CU's LDS or S, A exceed 64 (use LstmTorchHeads then)."""
+    wants_mlp_input, wants_parent_hidden = True, False
+
+    def __init__(self, representation, prediction, afterstate_prediction, afterstate_dynamics, dynamics, num_actions,
+                 support_size, device):
+        import numpy as np
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        trunks, (rep_w, rep_b) = lstm_trunks_from_modules(representation, prediction, afterstate_prediction,
+                                                          afterstate_dynamics, dynamics)
+        self.A, self.S = int(num_actions), int(support_size)
+        self.obs, self.L = int(rep_w.shape[1]), len(trunks[0][2])
+        d = _lib.LstmDesc(self.obs, self.A, self.S, self.L)
+        if self.lib.smz_lstm_layout(C.byref(d)) != 0:
+            raise ValueError("lstm heads outside the HIP kernel's limits (S, A <= 64, 1 <= L <= 4, trunks within LDS)")
+        self.desc = d
+        buf = np.zeros(d.total_floats, np.float32)
+
+        def put(idx, W, b):
+            """W [G, K] (torch layout) -> input-major, 4-way interleaved, row width G; b [G]."""
+            W = np.asarray(W, np.float32)
+            G, K = W.shape
+            K4 = (K + 3) & ~3
+            Wt = np.zeros((K4, G), np.float32)
+            Wt[:K] = W.T
+            buf[d.off[idx]:d.off[idx] + K4 * G] = Wt.reshape(K4 // 4, 4, G).transpose(0, 2, 1).reshape(-1)
+            buf[d.off[idx + 1]:d.off[idx + 1] + G] = np.asarray(b, np.float32)
+
+        f64 = lambda x: x.cpu().double().numpy()
+        for t, (w, b, layers) in enumerate(trunks):
+            O = layers[0][0].shape[0] // 4
+            keep = np.r_[0:O, 2 * O:4 * O]                     # gates i, g, o (f multiplies c0 = 0)
+            for l, (wi, bi, bh) in enumerate(layers):
+                wi, bi, bh = f64(wi)[keep], f64(bi)[keep], f64(bh)[keep]
+                if l == 0:      # no activation between the Linear and the first layer: fold it in
+                    W, bias = wi @ f64(w), wi @ f64(b) + bi + bh
+                else:
+                    W, bias = wi, bi + bh
+                put(2 * (t * _lib.LstmDesc.MAX_LAYERS + l), W, bias)
+        put(_lib.LstmDesc.REP, rep_w.cpu().numpy(), rep_b.cpu().numpy())
+        self.weights = torch.from_numpy(buf).to(self.device)
+        self._buf = {}
+
+    def _out(self, name, shape, dtype=torch.float32):
+        t = self._buf.get(name)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = self._buf[name] = torch.empty(*shape, dtype=dtype, device=self.device)
+        return t
+
+    def initial(self, obs):
+        B = obs.shape[0]
+        assert obs.dtype == torch.float32 and obs.is_contiguous() and obs.shape[1] == self.obs
+        hidden, policy = self._out("h0", (B, self.S)), self._out("p0", (B, self.A))
+        _lib.check(self.lib.smz_lstm_initial(C.byref(self.desc), _ptr(self.weights), _ptr(obs), _ptr(hidden),
+                                             _ptr(policy), B, _stream(self.device)))
+        return hidden, policy
+
+    def recurrent(self, engine):
+        x, branch = engine.mlp_input, engine.branch
+        B = x.shape[0]
+        assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == self.S + self.A
+        hidden, reward = self._out("h", (B, self.S)), self._out("r", (B,))
+        policy, value = self._out("p", (B, self.A)), self._out("v", (B,))
+        _lib.check(self.lib.smz_lstm_recurrent(C.byref(self.desc), _ptr(self.weights), _ptr(x), _ptr(branch),
+                                               _ptr(hidden), _ptr(reward), _ptr(policy), _ptr(value), B,
+                                               _stream(self.device)))
         return hidden, reward, policy, value
 
 

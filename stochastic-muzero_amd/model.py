@@ -16,8 +16,9 @@ import sys
 import numpy as np
 import torch
 
-from . import compat_mlp, compat_vision
-from .heads import MLP_ARRAYS, FusedMlpHeads, HipMlpHeads, HipMlpTileHeads, HipVisionHeads, ModuleHeads
+from . import compat_lstm, compat_mlp, compat_vision
+from .heads import (MLP_ARRAYS, FusedMlpHeads, HipLstmHeads, HipMlpHeads, HipMlpTileHeads, HipVisionHeads, LstmTorchHeads,
+                    ModuleHeads)
 
 _FUNCS = ("representation", "prediction", "afterstate_prediction", "afterstate_dynamics", "dynamics", "encoder")
 _FAMILY_MODULE = {"mlp_model": "neural_network_mlp_model", "lstm_model": "neural_network_lstm_model",
@@ -33,9 +34,13 @@ for _n in ("Representation_function", "Prediction_function", "Afterstate_predict
            "Afterstate_dynamics_function", "Dynamics_function", "Encoder_function", "Residual_block", "Down_sample",
            "Onehot_argmax"):
     getattr(compat_vision, _n).__module__ = "neural_network_vision_model"
+for _n in ("Representation_function", "Prediction_function", "Afterstate_prediction_function",
+           "Afterstate_dynamics_function", "Dynamics_function", "Encoder_function", "extract_tensor", "Onehot_argmax"):
+    getattr(compat_lstm, _n).__module__ = "neural_network_lstm_model"
 
 
-_COMPAT = {"neural_network_mlp_model": compat_mlp, "neural_network_vision_model": compat_vision}
+_COMPAT = {"neural_network_mlp_model": compat_mlp, "neural_network_vision_model": compat_vision,
+           "neural_network_lstm_model": compat_lstm}
 
 
 def _is_compat_class(cls):
@@ -45,7 +50,7 @@ def _is_compat_class(cls):
 
 
 class _compat_modules_bound:
-    """While inside: `neural_network_{mlp,vision}_model` resolve to this package's re-declarations, so that torch.save
+    """While inside: `neural_network_{mlp,vision,lstm}_model` resolve to this package's re-declarations, so that torch.save
     writes -- and torch.load of a reference checkpoint finds -- the class paths the reference's pickles carry.  Whatever
     was registered under those names before (the reference's real modules, when a process has imported them) is put
     back afterwards; nothing stays registered globally."""
@@ -121,9 +126,11 @@ class Muzero:
         self._heads_version = {}
         if load:
             return
-        if model_structure not in ("mlp_model", "vision_model"):
-            raise NotImplementedError("fresh construction is provided for mlp_model and vision_model; other "
+        if model_structure not in ("mlp_model", "vision_model", "lstm_model"):
+            raise NotImplementedError("fresh construction is provided for mlp_model, lstm_model and vision_model; other "
                                       "families load from checkpoints written by the reference")
+        if model_structure == "lstm_model" and self.number_of_hidden_layer < 1:
+            raise ValueError("lstm_model: number_of_hidden_layer is the LSTM's num_layers and must be at least 1")
         n_act = int(action_space_dimensions)
         self.action_dictionnary = list(action_map) if action_map is not None else list(range(n_act))
         self.action_dimension = len(self.action_dictionnary)
@@ -131,13 +138,14 @@ class Muzero:
             family = compat_vision
             self.observation_dimension = compat_vision.FRAME          # muzero_model.py:400-404: fixed for vision
         else:
-            family = compat_mlp
+            family = compat_lstm if model_structure == "lstm_model" else compat_mlp
             self.observation_dimension = int(observation_space_dimensions)
         kw = dict(state_dimension=self.state_dimension, action_dimension=self.action_dimension,
                   observation_space_dimensions=self.observation_dimension,
                   hidden_layer_dimensions=self.hidden_layer_dimension, number_of_hidden_layer=self.number_of_hidden_layer)
         # construction order and generator draws = muzero_model.py:300-335 (compat_mlp._unused_draws), so an equal torch
-        # seed gives the reference's initial weights (pinned for both families by goldens the reference initialised)
+        # seed gives the reference's initial weights (pinned for every family by goldens the reference initialised; the
+        # lstm family's nn.LSTM parameters keep torch's default initialisation: weights_init touches Linear layers only)
         self.representation_function = family.Representation_function(**kw)
         self.prediction_function = family.Prediction_function(**kw)
         self.afterstate_prediction_function = family.Afterstate_prediction_function(**kw)
@@ -268,9 +276,9 @@ class Muzero:
         self._heads_version = {}
 
     def heads(self, device, instance=0, backend="auto"):
-        """Batched evaluator on `device`.  backend: "hip" = the fused LDS-resident HIP kernel (mlp_model only, when
-        the networks fit a CU's LDS), "torch" = torch-ROCm GEMMs + HIP epilogues, "auto" = hip when possible, else (mlp_model) the wide tile
-        kernel for the recurrent networks when the shape is within its limits, else torch.
+        """Batched evaluator on `device`.  backend: "hip" = the fused LDS-resident HIP kernels (mlp_model and lstm_model when
+        the networks fit a CU's LDS; vision_model), "torch" = torch-ROCm GEMMs + HIP epilogues, "auto" = hip when possible,
+        else (mlp_model) the wide tile kernel for the recurrent networks when the shape is within its limits, else torch.
         `instance` distinguishes evaluators that must not share output buffers (one per concurrent stream group)."""
         key = (str(device), instance, backend)
         version = self.weights_version()
@@ -303,6 +311,17 @@ class Muzero:
                             H=self.hidden_layer_dimension, L=self.number_of_hidden_layer)
                 assert set(n + s for n in MLP_ARRAYS for s in ("_w", "_b")) <= set(arrays)
                 self._heads[key] = FusedMlpHeads(arrays, dims, device)
+            elif self.model_structure == "lstm_model":
+                mods = [getattr(self, f + "_function") for f in _FUNCS[:5]]
+                kw = dict(num_actions=self.action_dimension, support_size=self.state_dimension, device=device)
+                if backend in ("auto", "hip"):
+                    try:
+                        self._heads[key] = HipLstmHeads(*mods, **kw)
+                        return self._heads[key]
+                    except ValueError:
+                        if backend == "hip":
+                            raise
+                self._heads[key] = LstmTorchHeads(*mods, **kw)
             elif self.model_structure == "vision_model" and backend in ("auto", "hip"):
                 mods = [getattr(self, f + "_function") for f in _FUNCS[:5]]
                 self._heads[key] = HipVisionHeads(*mods, num_actions=self.action_dimension,

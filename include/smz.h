@@ -33,6 +33,7 @@ extern "C" {
 
 #define SMZ_ABI_VERSION 1
 #define SMZ_MAX_ACTIONS 32 /* action_dimension limit of this build (per-lane scratch is sized by it) */
+#define SMZ_MAX_ACTIONS_LARGE 1024 /* action_dimension limit of smz_create_large_actions (one wavefront per tree) */
 #define SMZ_MAX_PLAYER_CYCLE 32 /* longest turn cycle smz_set_players accepts */
 #define SMZ_MT_WORDS 624   /* MT19937 state words per tree */
 
@@ -89,6 +90,12 @@ typedef struct {
 /* [sync] Allocates all device state for cfg->num_trees trees.  Replaces Monte_carlo_tree_search.__init__/reset
  * (mcts:76-177).  SMZ_ERR_INVALID where the reference asserts. */
 int smz_create(const smz_config *cfg, smz_handle **out);
+/* [sync] The same handle for 1 <= num_actions <= SMZ_MAX_ACTIONS_LARGE (SMZ_ERR_INVALID outside): the step-wise calls
+ * (smz_root_init, smz_select, smz_expand_backup(_select), smz_act) run kernels with one wavefront per tree and the A-wide
+ * arrays in LDS; results, tree layout and random-word consumption are those of an smz_create handle.  The single-launch
+ * searches (smz_search_mlp*, smz_search_vision*) and smz_enable_stats return SMZ_ERR_TOO_LARGE on such a handle.  Path
+ * records name a child as (block << 10 | slot) instead of (block << 8 | slot); smz_debug_dump_tree decodes either. */
+int smz_create_large_actions(const smz_config *cfg, smz_handle **out);
 /* [sync] */
 int smz_destroy(smz_handle *h);
 int smz_abi_version(void);

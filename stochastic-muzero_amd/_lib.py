@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("SMZ_LIB_PATH") or os.path.join(_HERE, "libsmz.so")   
 SMZ_OK, SMZ_ERR_INVALID, SMZ_ERR_HIP, SMZ_ERR_NOMEM, SMZ_ERR_STATE, SMZ_ERR_TOO_LARGE = 0, -1, -2, -3, -4, -5
 RNG_MT19937_NUMPY, RNG_PHILOX = 0, 1
 MAX_ACTIONS = 32
+MAX_ACTIONS_LARGE = 1024      # smz_create_large_actions: 33..1024 actions run the wave-per-tree kernels
 
 
 class SmzError(RuntimeError):
@@ -69,6 +70,7 @@ _P = C.c_void_p
 # every exported symbol of include/smz.h: name -> (restype, argtypes)
 SIGNATURES = {
     "smz_create": (C.c_int, [C.POINTER(Config), C.POINTER(_P)]),
+    "smz_create_large_actions": (C.c_int, [C.POINTER(Config), C.POINTER(_P)]),
     "smz_destroy": (C.c_int, [_P]),
     "smz_abi_version": (C.c_int, []),
     "smz_build_features": (C.c_int, []),

@@ -267,6 +267,21 @@ __device__ inline T np_sum(const T *a, int n) {
     return res;
 }
 
+// ndarray.sum() of n <= 1024 contiguous elements (the large-action kernels): numpy's pairwise summation -- np_sum's block up to
+// 128 elements, above that the sum of the two halves, the first rounded down to a multiple of 8.  D bounds the recursion at
+// compile time (no call stack): four halvings bring any n <= 1024 to a block.
+template <typename T, int D = 4>
+__device__ inline T np_sum_pairwise(const T *a, int n) {
+    if constexpr (D == 0) {
+        return np_sum<T, 8>(a, n);
+    } else {
+        if (n <= 128) return np_sum<T, 8>(a, n);
+        int n2 = n / 2;
+        n2 -= n2 % 8;
+        return np_sum_pairwise<T, D - 1>(a, n2) + np_sum_pairwise<T, D - 1>(a + n2, n - n2);
+    }
+}
+
 // cdf = cumsum(p); cdf /= cdf[-1]; searchsorted(cdf, u, side='right')  == number of entries <= u
 template <int MAXA>
 __device__ inline int sample_cdf(const double *p, int n, double u) {
@@ -421,6 +436,20 @@ __device__ inline double legacy_gamma(RNG &rng, double shape) {
             if (X <= (V + Y)) return X;
         }
     }
+}
+
+// One round of legacy_gamma's rejection loop for shape < 1 (shape != 0), from the round's two uniforms: true, with the sample in
+// x, when the round accepts.  The rounds of a gamma are independent of each other and draw four words each, so consecutive
+// rounds can be evaluated side by side: the gammas of a stream are its accepting rounds, in order (the large-action kernels'
+// Dirichlet noise).
+__device__ inline bool legacy_gamma_round(double U, double u2, double shape, double &x) {
+    // (straight-line: one log for V, one for Y, one pow -- each operand as legacy_gamma forms it on its branch)
+    const bool low = U <= 1.0 - shape;
+    const double V = -smz_glibc_log(1.0 - u2);
+    const double Y = low ? 0.0 : -smz_glibc_log((1.0 - U) / shape);
+    const double X = smz_glibc_pow(low ? U : 1.0 - shape + shape * Y, 1.0 / shape);
+    x = X;
+    return low ? X <= V : X <= (V + Y);
 }
 
 // p = (policy + 1e-12) / sum, float32 (monte_carlo_tree_search.py:205-206, 291-292)

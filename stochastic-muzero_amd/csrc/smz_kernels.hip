@@ -1596,6 +1596,7 @@ struct smz_handle {
     std::vector<void *> allocs;
     char last_kernel[96];      // the single-launch search instantiation launched last, as rocprofv3 prints it (smz_last_kernel)
     uint32_t *d_player_neg;    // [SMZ_MAX_PLAYER_CYCLE] sign masks of smz_set_players (allocated by its first multi-player call)
+    bool large_actions;        // smz_create_large_actions: the step-wise calls run the wave-per-tree kernels (smz_large_actions.hip)
 };
 
 // the last-error text is shared by the translation units this file is compiled into (SMZ_PART)
@@ -1697,6 +1698,22 @@ int launch_check() {
 
 }  // namespace
 
+// the step-wise calls of a large-action handle (defined in smz_large_actions.hip)
+int smz_internal_la_root_init(smz_handle *h, const float *hidden_dev, const float *policy_dev, const double *noise_override_dev,
+                              int train, smz_stream stream);
+int smz_internal_la_select(smz_handle *h, float *parent_hidden_dev, int32_t *last_action_dev, uint8_t *branch_dev,
+                           float *mlp_input_dev, smz_stream stream);
+int smz_internal_la_expand_backup(smz_handle *h, const float *hidden_dev, const float *reward_dev, const float *policy_dev,
+                                  const float *value_dev, smz_stream stream);
+int smz_internal_la_act(smz_handle *h, const Params &P, double temperature, int32_t *action_dev, double *policy_dev,
+                        double *child_visits_dev, float *root_value_dev, smz_stream stream);
+
+#if SMZ_PART == 0 || SMZ_PART == 1
+namespace {
+int create_handle(const smz_config *cfg, smz_handle **out, bool large_actions);
+}
+#endif
+
 extern "C" {
 
 #if SMZ_PART == 0 || SMZ_PART == 1
@@ -1710,7 +1727,12 @@ int smz_last_kernel(const smz_handle *h, char *buf, int cap) {
     return (int)strlen(h->last_kernel);
 }
 
-int smz_create(const smz_config *cfg, smz_handle **out) {
+int smz_create(const smz_config *cfg, smz_handle **out) { return create_handle(cfg, out, false); }
+int smz_create_large_actions(const smz_config *cfg, smz_handle **out) { return create_handle(cfg, out, true); }
+}  // extern "C"
+
+namespace {
+int create_handle(const smz_config *cfg, smz_handle **out, bool large_actions) {
     if (!cfg || !out) return fail(SMZ_ERR_INVALID, "smz_create: null argument%s");
     *out = nullptr;
     // hyper-parameter checks of monte_carlo_tree_search.py:148-173
@@ -1724,8 +1746,10 @@ int smz_create(const smz_config *cfg, smz_handle **out) {
     if (cfg->max_action_sample < 1) return fail(SMZ_ERR_INVALID, "maxium_action_sample must be an int >= 1%s");
     if (cfg->num_simulations < 0) return fail(SMZ_ERR_INVALID, "num_simulations must be an int >= 0%s");
     if (cfg->num_trees < 1) return fail(SMZ_ERR_INVALID, "num_trees must be >= 1%s");
-    if (cfg->num_actions < 1 || cfg->num_actions > SMZ_MAX_ACTIONS)
+    if (!large_actions && (cfg->num_actions < 1 || cfg->num_actions > SMZ_MAX_ACTIONS))
         return fail(SMZ_ERR_INVALID, "num_actions must be in [1, SMZ_MAX_ACTIONS]%s");
+    if (large_actions && (cfg->num_actions < 1 || cfg->num_actions > SMZ_MAX_ACTIONS_LARGE))
+        return fail(SMZ_ERR_INVALID, "num_actions must be in [1, SMZ_MAX_ACTIONS_LARGE] (smz_create_large_actions)%s");
     if (cfg->hidden_size < 0) return fail(SMZ_ERR_INVALID, "hidden_size must be >= 0%s");
     if (cfg->num_simulations > 32000) return fail(SMZ_ERR_INVALID, "num_simulations above 32000 is not supported%s");
     if (cfg->rng_mode != SMZ_RNG_MT19937_NUMPY && cfg->rng_mode != SMZ_RNG_PHILOX)
@@ -1746,6 +1770,7 @@ int smz_create(const smz_config *cfg, smz_handle **out) {
     h->root_ready = h->selected = false;
     h->pow_valid = false;
     h->d_player_neg = nullptr;
+    h->large_actions = large_actions;
     h->pow_T = 0.0;
     h->stats_on = false;
 
@@ -1828,7 +1853,9 @@ int smz_create(const smz_config *cfg, smz_handle **out) {
     *out = h;
     return SMZ_OK;
 }
+}  // namespace
 
+extern "C" {
 int smz_destroy(smz_handle *h) {
     if (!h) return SMZ_OK;
     DeviceGuard guard(h->cfg.device);
@@ -1946,6 +1973,11 @@ int smz_root_init(smz_handle *h, const float *hidden_dev, const float *policy_de
     if (train && h->cfg.num_simulations > 0 && !(h->cfg.root_dirichlet_alpha > 0))
         return fail(SMZ_ERR_INVALID, "root_dirichlet_alpha must be > 0 to draw noise (numpy raises ValueError)%s");
     DeviceGuard guard(h->cfg.device);
+    if (h->large_actions) {
+        h->root_ready = true;
+        h->selected = false;
+        return smz_internal_la_root_init(h, hidden_dev, policy_dev, noise_override_dev, train, stream);
+    }
     SMZ_DISPATCH(h->maxa, hipLaunchKernelGGL((k_root_init<MA>), wave_grid(h->P), dim3(kWave), tree_lds_bytes(h->P), (hipStream_t)stream,
                                              h->P, hidden_dev, policy_dev, noise_override_dev, train));
     h->root_ready = true;
@@ -1958,6 +1990,10 @@ int smz_select(smz_handle *h, float *parent_hidden_dev, int32_t *last_action_dev
     if (!h) return fail(SMZ_ERR_INVALID, "smz_select: null handle%s");
     if (!h->root_ready) return fail(SMZ_ERR_STATE, "smz_select before smz_root_init%s");
     DeviceGuard guard(h->cfg.device);
+    if (h->large_actions) {
+        h->selected = true;
+        return smz_internal_la_select(h, parent_hidden_dev, last_action_dev, branch_dev, mlp_input_dev, stream);
+    }
     SMZ_DISPATCH2_AEX(h->maxa, h->K, h->P.A == h->maxa && !h->P.philox, hipLaunchKernelGGL((k_select<MA, KS, AEX>), wave_grid(h->P), dim3(kWave), tree_lds_bytes(h->P), (hipStream_t)stream, h->P,
                                              parent_hidden_dev, last_action_dev, branch_dev, mlp_input_dev));
     h->selected = true;
@@ -1969,6 +2005,10 @@ int smz_expand_backup(smz_handle *h, const float *hidden_dev, const float *rewar
     if (!h || !policy_dev || !value_dev) return fail(SMZ_ERR_INVALID, "smz_expand_backup: null argument%s");
     if (!h->selected) return fail(SMZ_ERR_STATE, "smz_expand_backup without a preceding smz_select%s");
     DeviceGuard guard(h->cfg.device);
+    if (h->large_actions) {
+        h->selected = false;
+        return smz_internal_la_expand_backup(h, hidden_dev, reward_dev, policy_dev, value_dev, stream);
+    }
     if (h->P.n_cycle > 1) {     // multi-player handle (smz_set_players)
         SMZ_DISPATCH2_AEX(h->maxa, h->K, h->P.A == h->maxa && !h->P.philox, hipLaunchKernelGGL((k_expand_backup_mp<MA, KS, false, AEX>), wave_grid(h->P), dim3(kWave), tree_lds_bytes(h->P),
                                                  (hipStream_t)stream, h->P, hidden_dev, reward_dev, policy_dev, value_dev,
@@ -1991,6 +2031,11 @@ int smz_expand_backup_select(smz_handle *h, const float *hidden_dev, const float
     if (!h || !policy_dev || !value_dev) return fail(SMZ_ERR_INVALID, "smz_expand_backup_select: null argument%s");
     if (!h->selected) return fail(SMZ_ERR_STATE, "smz_expand_backup_select without a preceding smz_select%s");
     DeviceGuard guard(h->cfg.device);
+    if (h->large_actions) {      // two launches: the same trees and words as the fused kernel
+        const int rc = smz_internal_la_expand_backup(h, hidden_dev, reward_dev, policy_dev, value_dev, stream);
+        if (rc != SMZ_OK) return rc;
+        return smz_internal_la_select(h, parent_hidden_dev, last_action_dev, branch_dev, mlp_input_dev, stream);
+    }
     const bool mp = h->P.n_cycle > 1;      // multi-player handle (smz_set_players)
     if (h->P.philox && h->P.A == h->maxa && h->maxa <= 4) {       // Philox handles, exact action count: the specialised kernel too
 #define SMZ_EBS_PHX(KERNEL, MA, KS)                                                                                          \
@@ -2249,6 +2294,7 @@ extern "C" {
 #if SMZ_PART != 4 && SMZ_PART != 6
 int smz_search_mlp(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, int train,
                    smz_stream stream) {
+    if (h && h->large_actions) return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp: large-action handles search step-wise only%s");
     if (h && h->P.n_cycle > 1) return fail(SMZ_ERR_INVALID, "smz_search_mlp: multi-player handles search step-wise only%s");
     return smz_internal_search_launch_narrow(h, desc, weights_dev, obs_dev, train,
                                              SearchActArgs{0.0, nullptr, nullptr, nullptr, nullptr, EnvStep{}}, nullptr, stream);
@@ -2257,6 +2303,7 @@ int smz_search_mlp(smz_handle *h, const smz_mlp_desc *desc, const float *weights
 int smz_search_mlp_act(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, int train,
                        double temperature, const double *pow_table_host, int32_t *action_dev, double *policy_dev,
                        double *child_visits_dev, float *root_value_dev, smz_stream stream) {
+    if (h && h->large_actions) return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp_act: large-action handles search step-wise only%s");
     if (!action_dev || !policy_dev || !child_visits_dev) return fail(SMZ_ERR_INVALID, "smz_search_mlp_act: null output%s");
     if (h && h->P.n_cycle > 1) return fail(SMZ_ERR_INVALID, "smz_search_mlp_act: multi-player handles search step-wise only%s");
     return smz_internal_search_launch_narrow(h, desc, weights_dev, obs_dev, train,
@@ -2269,6 +2316,8 @@ int smz_search_mlp_act_cartpole(smz_handle *h, const smz_mlp_desc *desc, const f
                                 double temperature, const double *pow_table_host, int32_t *action_dev, double *policy_dev,
                                 double *child_visits_dev, float *root_value_dev, const smz_cartpole_env *env,
                                 smz_stream stream) {
+    if (h && h->large_actions)
+        return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp_act_cartpole: large-action handles search step-wise only%s");
     if (!action_dev || !policy_dev || !child_visits_dev || !root_value_dev || !env || !env->state_dev || !env->obs_dev)
         return fail(SMZ_ERR_INVALID, "smz_search_mlp_act_cartpole: null argument%s");
     if (!h || !desc || h->P.A != 2 || desc->obs != 4)
@@ -2323,6 +2372,7 @@ int smz_act(smz_handle *h, double temperature, const double *pow_table_host, int
         }
         P.pow_table = h->d_pow;
     }
+    if (h->large_actions) return smz_internal_la_act(h, P, temperature, action_dev, policy_dev, child_visits_dev, root_value_dev, stream);
     SMZ_DISPATCH(h->maxa, hipLaunchKernelGGL((k_act<MA>), tree_grid(P.B), dim3(kWave), 0, (hipStream_t)stream, P, temperature,
                                              action_dev, policy_dev, child_visits_dev, root_value_dev));
     return launch_check();
@@ -2602,8 +2652,9 @@ int smz_debug_dump_tree(smz_handle *h, int tree, smz_node_view *nodes, int cap, 
         std::vector<uint4> recs((size_t)hdr.path_len);
         HIP_TRY(hipMemcpy2D(recs.data(), sizeof(uint4), P.path + tree, (size_t)P.B * sizeof(uint4), sizeof(uint4), (size_t)hdr.path_len, hipMemcpyDeviceToHost));
         path_out[0] = 0;
+        const int sb = h->large_actions ? 10 : 8;          // slot bits of a path record (smz_large_actions.hip: kLaSlotBits)
         for (int i = 0; i < hdr.path_len && i + 1 < cap_path; i++) {
-            const int blk = (int)recs[i].x >> 8, slot = (int)recs[i].x & 0xff;
+            const int blk = (int)recs[i].x >> sb, slot = (int)recs[i].x & ((1 << sb) - 1);
             path_out[i + 1] = blk == 0 ? 1 + slot : 1 + A + (blk - 1) * K + slot;
         }
     }
@@ -2635,6 +2686,8 @@ int smz_get_philox_position(smz_handle *h, int tree, uint32_t *block_out, int *i
 
 int smz_enable_stats(smz_handle *h, int on) {
     if (!h) return fail(SMZ_ERR_INVALID, "smz_enable_stats: null handle%s");
+    if (h->large_actions && on)
+        return fail(SMZ_ERR_TOO_LARGE, "smz_enable_stats: the large-action kernels keep no level statistics%s");
     h->stats_on = on != 0;
     h->P.stats = h->stats_on ? h->d_stats : nullptr;
     return SMZ_OK;

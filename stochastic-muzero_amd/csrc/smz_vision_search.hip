@@ -631,6 +631,7 @@ __global__ void __launch_bounds__(kVW *kWave) SMZ_VISION_OCC k_search_vision(Par
 
 int search_vision_launch(smz_handle *h, const smz_vision_desc *desc, const float *weights_dev, const float *hidden0_dev,
                          const float *policy0_dev, int train, ActOut act, const double *pow_table_host, smz_stream stream) {
+    if (h && h->large_actions) return fail(SMZ_ERR_TOO_LARGE, "smz_search_vision: large-action handles search step-wise only%s");
     if (!h || !desc || !weights_dev || !hidden0_dev || !policy0_dev) return fail(SMZ_ERR_INVALID, "smz_search_vision: null argument%s");
     if (h->P.n_cycle > 1) return fail(SMZ_ERR_INVALID, "smz_search_vision: multi-player handles search step-wise only%s");
     smz_vision_desc t = *desc;

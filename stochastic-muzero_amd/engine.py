@@ -32,7 +32,9 @@ def _ptr(t):
 class SearchEngine:
     def __init__(self, num_trees, num_actions, hidden_size, num_simulations=10, maxium_action_sample=2,
                  pb_c_base=19652, pb_c_init=1.25, discount=0.95, root_dirichlet_alpha=0.25,
-                 root_exploration_fraction=0.25, device=None, rng_mode=_lib.RNG_MT19937_NUMPY):
+                 root_exploration_fraction=0.25, device=None, rng_mode=_lib.RNG_MT19937_NUMPY, large_actions=False):
+        """large_actions: create through smz_create_large_actions -- up to MAX_ACTIONS_LARGE actions, one wavefront per tree
+        (step-wise calls only: search_mlp / search_vision refuse such an engine)."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("SearchEngine needs a HIP device (torch.cuda.is_available() is False); "
@@ -46,7 +48,9 @@ class SearchEngine:
                                float(pb_c_init), float(discount), float(root_dirichlet_alpha),
                                float(root_exploration_fraction), int(rng_mode), int(self.device.index))
         h = C.c_void_p()
-        _lib.check(self.lib.smz_create(C.byref(self.cfg), C.byref(h)))
+        self.large_actions = bool(large_actions)
+        create = self.lib.smz_create_large_actions if self.large_actions else self.lib.smz_create
+        _lib.check(create(C.byref(self.cfg), C.byref(h)))
         self.h = h
         self.N = self.lib.smz_node_capacity(self.h)
         tab = pb_c_table(int(pb_c_base), float(pb_c_init), self.sims + 2)

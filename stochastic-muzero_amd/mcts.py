@@ -161,7 +161,8 @@ class BatchedMCTS(_Hyper):
             if self.engine is not None:
                 self.engine.close()
             self.engine = SearchEngine(self.num_trees, num_actions, hidden_size, device=self.device,
-                                       rng_mode=self.rng_mode, **self._engine_kwargs())
+                                       rng_mode=self.rng_mode, large_actions=num_actions > _lib.MAX_ACTIONS,
+                                       **self._engine_kwargs())
             if getattr(self, "_active", None) is not None:
                 self.engine.set_active(self._active)
             self._bind_players(self.engine)
@@ -261,6 +262,9 @@ class BatchedMCTS(_Hyper):
         self._recorded = False
         if self.n_cycle > 1:
             # the multi-player backup exists in the step-wise kernels only (the single launch refuses such a handle)
+            return self._run_stepwise(observations, heads, train)
+        if int(getattr(heads, "A", 0)) > _lib.MAX_ACTIONS:
+            # more actions than the per-lane kernels take: the wave-per-tree step-wise kernels (no single launch)
             return self._run_stepwise(observations, heads, train)
         # (single_launch_max_trees: where the step-wise kernels overtake the single launch)
         if (self.single_launch and isinstance(getattr(heads, "desc", None), _lib.MlpDesc) and self._single is not False
@@ -400,7 +404,7 @@ class Monte_carlo_tree_search(_Hyper):
         h0_flat = torch.as_tensor(h0).detach().reshape(1, -1).float()
         A, S = int(np.asarray(policy).shape[-1]), int(h0_flat.shape[1])
         if self._engine is None or (self._engine.A, self._engine.S) != (A, S):
-            self._engine = SearchEngine(1, A, S, **self._engine_kwargs())
+            self._engine = SearchEngine(1, A, S, large_actions=A > _lib.MAX_ACTIONS, **self._engine_kwargs())
             self._bind_players(self._engine)
         eng = self._engine
         if self.n_cycle > 1:

@@ -491,7 +491,9 @@ class HipLstmHeads:
     """`lstm_model` heads evaluated by hand-written HIP kernels (smz_lstm_initial / smz_lstm_recurrent, csrc/smz_lstm.hip):
     the seven recurrent trunks packed once into the LDS layout of smz_lstm_desc (include/smz.h), each trunk's input Linear
     folded into its first LSTM layer on the host (float64 products, rounded once), forget gates and W_hh dropped (zero
-    state).  Raises ValueError when the trunks do not fit a CU's LDS or S, A exceed 64 (use LstmTorchHeads then)."""
+    state).  Raises ValueError outside smz_lstm_layout's limits (use LstmTorchHeads then): obs <= 4096, A <= 64, 1 <= L <= 4, and
+    the seven trunks plus four waves of scratch within 160 KB of LDS, which caps S at 48 -- (obs 9, A 4, S 48, L 1) is the last
+    shape that fits (159,712 B); (9, 4, 49, 1) needs 175,024 B and (4, 2, 31, 3) 197,616 B."""
     wants_mlp_input, wants_parent_hidden = True, False
 
     def __init__(self, representation, prediction, afterstate_prediction, afterstate_dynamics, dynamics, num_actions,
@@ -505,7 +507,11 @@ class HipLstmHeads:
         self.obs, self.L = int(rep_w.shape[1]), len(trunks[0][2])
         d = _lib.LstmDesc(self.obs, self.A, self.S, self.L)
         if self.lib.smz_lstm_layout(C.byref(d)) != 0:
-            raise ValueError("lstm heads outside the HIP kernel's limits (S, A <= 64, 1 <= L <= 4, trunks within LDS)")
+            # (lds_bytes stays 0 when a dimension is outside the limits: the layout returns before it sizes anything)
+            needs = f", needs {d.lds_bytes} B" if d.lds_bytes > 0 else ""
+            raise ValueError("lstm heads outside the HIP kernel's limits (obs <= 4096, A <= 64, 1 <= L <= 4, trunks + scratch "
+                             f"within 160 KB of LDS, which caps S at 48; this net: obs {self.obs}, A {self.A}, S {self.S}, "
+                             f"L {self.L}{needs})")
         self.desc = d
         buf = np.zeros(d.total_floats, np.float32)
 

@@ -42,7 +42,8 @@ def _p(t):
     return C.c_void_p(t.data_ptr())
 
 
-@pytest.mark.parametrize("B,S", [(1, 31), (4096, 31), (1000, 30), (777, 61), (64, 5)])
+# (rows wider than one 64-lane group loop inside the kernels: S 65 and 601, A 65 .. 1024; S = 1 and A = 1 are the degenerate rows)
+@pytest.mark.parametrize("B,S", [(1, 31), (4096, 31), (1000, 30), (777, 61), (64, 5), (300, 65), (7, 601), (9, 1)])
 def test_support_decode(B, S):
     import stochastic_muzero_amd as smz
     lib = smz._lib.load()
@@ -56,7 +57,7 @@ def test_support_decode(B, S):
     assert gu.decode_steps(out.cpu().numpy(), _ref_decode(logits).cpu().numpy()).max() <= 2 * gu.DECODE_BOUND_STEPS   # torch-ROCm float32
 
 
-@pytest.mark.parametrize("B,A", [(4096, 2), (513, 4), (100, 18)])
+@pytest.mark.parametrize("B,A", [(4096, 2), (513, 4), (100, 18), (257, 64), (100, 65), (33, 129), (64, 1000), (5, 1024), (3, 1)])
 def test_policy_softmax(B, A):
     import stochastic_muzero_amd as smz
     lib = smz._lib.load()
@@ -65,9 +66,10 @@ def test_policy_softmax(B, A):
     out = torch.empty(B, A, device="cuda")
     smz._lib.check(lib.smz_policy_softmax(_p(logits), A, _p(out), B, _s()))
     torch.testing.assert_close(out, torch.softmax(logits, -1), rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(out.double(), torch.softmax(logits.double(), -1), rtol=1e-5, atol=1e-6)
 
 
-@pytest.mark.parametrize("B,A,S", [(4096, 2, 31), (300, 4, 16), (65, 11, 7)])
+@pytest.mark.parametrize("B,A,S", [(4096, 2, 31), (300, 4, 16), (65, 11, 7), (130, 100, 31), (65, 1000, 65)])
 def test_dynamics_and_prediction_epilogues(B, A, S):
     import stochastic_muzero_amd as smz
     lib = smz._lib.load()

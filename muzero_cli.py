@@ -47,12 +47,15 @@ def parse_argv(argv):
 
 def mcts_kwargs(config, num_simulations=None):
     m = config["monte_carlo_tree_search"]
-    return dict(pb_c_base=m["pb_c_base"], pb_c_init=m["pb_c_init"], discount=m["discount"],
-                root_dirichlet_alpha=m["root_dirichlet_alpha"],
-                root_exploration_fraction=m["root_exploration_fraction"],
-                num_simulations=m["num_simulations"] if num_simulations is None else num_simulations,
-                maxium_action_sample=m["maxium_action_sample"], number_of_player=m["number_of_player"],
-                custom_loop=m["custom_loop"])
+    kw = dict(pb_c_base=m["pb_c_base"], pb_c_init=m["pb_c_init"], discount=m["discount"],
+              root_dirichlet_alpha=m["root_dirichlet_alpha"],
+              root_exploration_fraction=m["root_exploration_fraction"],
+              num_simulations=m["num_simulations"] if num_simulations is None else num_simulations,
+              maxium_action_sample=m["maxium_action_sample"], number_of_player=m["number_of_player"],
+              custom_loop=m["custom_loop"])
+    if "lstm_single_launch" in m:       # (not a key of the reference's configs) lstm_model searches in one launch: BatchedMCTS
+        kw["lstm_single_launch"] = bool(m["lstm_single_launch"])
+    return kw
 
 
 def make_env(name, num_envs, device, seed, limit=0, on_end="continue"):

@@ -12,90 +12,17 @@
 #include <stdint.h>
 
 #include "../../include/smz.h"
-#include "smz_mlp_device.hpp"
+#include "smz_lstm_device.hpp"
 
 using namespace smz_mlp;
+using namespace smz_lstm;      // trunks, row body and LDS scratch map: shared with the whole-search kernel (smz_lstm_search.hip)
 
 namespace {
 
 extern __shared__ float4 smz_lstm_lds4[];
 
 constexpr int kLdsBytes = 160 * 1024;
-constexpr int kWavesPerWg = 4;        // ~67 KB of trunks (CartPole shape) + 4 waves of scratch: two workgroups per CU
-constexpr int kMaxUnits = 64;         // one LSTM unit per lane
 constexpr int kMaxObs = 4096;
-enum { T_DYN_RW = 0, T_DYN_ST, T_ADY_ST, T_PRE_POL, T_PRE_VAL, T_APR_POL, T_APR_VAL };
-
-__host__ __device__ inline int w_index(int t, int l) { return 2 * (t * SMZ_LSTM_MAX_LAYERS + l); }
-
-// per-wave LDS scratch: input row | gate pre-activations (3 x 64) | layer output | scaled state (prediction input)
-__host__ __device__ inline int scratch_floats(int in_width) { return up4(in_width) + 3 * kMaxUnits + 2 * kMaxUnits; }
-
-__device__ inline float lstm_sigmoid(float x) { return 1.f / (1.f + smz_exp(-x)); }
-// |x| >= 0.5: 1 - 2 / (e^2x + 1), which saturates to +-1 without overflow (e^2x = inf gives 1, e^2x = 0 gives -1).  Below,
-// that form loses the low bits of a small result to the cancellation (13 ulp on the logits of a freshly initialised net,
-// whose gate pre-activations are ~0.05), so the odd Taylor series takes over: < 1 ulp on [-0.5, 0.5] in float32.
-__device__ inline float lstm_tanh(float x) {
-    if (fabsf(x) >= 0.5f) return 1.f - 2.f / (smz_exp(2.f * x) + 1.f);
-    const float x2 = x * x;
-    float p = -443861162.f / 1856156927625.f;
-    p = p * x2 + 6404582.f / 10854718875.f;
-    p = p * x2 + -929569.f / 638512875.f;
-    p = p * x2 + 21844.f / 6081075.f;
-    p = p * x2 + -1382.f / 155925.f;
-    p = p * x2 + 62.f / 2835.f;
-    p = p * x2 + -17.f / 315.f;
-    p = p * x2 + 2.f / 15.f;
-    p = p * x2 + -1.f / 3.f;
-    return x + (x * x2) * p;
-}
-
-// gbuf[c] = bias[c] + sum_k W[k][c] * in[k] for c < G (row width G, in zero-padded to K4).  Columns past G read the next
-// pieces of the image (or its zero slack): finite or not, they are never stored.
-template <int U>
-__device__ inline void gate_columns(const float *W, const float *bias, const float *in, int K4, int G, int lane, float *gbuf) {
-    const float *w[1] = {W}, *b[1] = {bias}, *a[1] = {in};
-    float acc[1][U];
-    dense<U, 1>(w, b, a, K4, G, lane, acc);
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const int c = lane + kWave * u;
-        if (c < G) gbuf[c] = acc[0][u];
-    }
-}
-
-// One trunk (all L layers) on the row `in` (K inputs, zero-padded to up4(K)).  Returns unit `lane`'s output of the last
-// layer (0 for lane >= O); hbuf receives it too, zero-padded to up4(O).
-__device__ inline float lstm_trunk(const float *img, const smz_lstm_desc &d, int t, const float *in, int K, int O,
-                                   float *gbuf, float *hbuf, int lane) {
-    const int G = 3 * O;
-    float h = 0.f;
-    for (int l = 0; l < d.L; l++) {
-        const float *W = img + d.off[w_index(t, l)], *bias = img + d.off[w_index(t, l) + 1];
-        const float *src = l == 0 ? in : hbuf;
-        const int K4 = up4(l == 0 ? K : O);
-        if (G <= kWave) gate_columns<1>(W, bias, src, K4, G, lane, gbuf);
-        else if (G <= 2 * kWave) gate_columns<2>(W, bias, src, K4, G, lane, gbuf);
-        else gate_columns<3>(W, bias, src, K4, G, lane, gbuf);
-        lds_sync();
-        h = 0.f;
-        if (lane < O) {
-            const float c = lstm_sigmoid(gbuf[lane]) * lstm_tanh(gbuf[O + lane]);
-            h = lstm_sigmoid(gbuf[2 * O + lane]) * lstm_tanh(c);
-        }
-        if (lane < up4(O)) hbuf[lane] = h;
-        lds_sync();
-    }
-    return h;
-}
-
-// the image's [0, n) floats to the same offsets in LDS (n and the base a multiple of 4 floats)
-__device__ inline void stage(float *lds, const float *weights, int n) {
-    const float4 *src = reinterpret_cast<const float4 *>(weights);
-    float4 *dst = reinterpret_cast<float4 *>(lds);
-    for (int i = threadIdx.x; i < n / 4; i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
-}
 
 __global__ void __launch_bounds__(kWavesPerWg * 64) k_lstm_recurrent(smz_lstm_desc d, const float *weights, const float *x,
                                                                      const uint8_t *branch, float *hidden_out, float *reward_out,
@@ -106,30 +33,15 @@ __global__ void __launch_bounds__(kWavesPerWg * 64) k_lstm_recurrent(smz_lstm_de
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const int S = d.S, A = d.A, K = S + A;
     float *xin = lds + d.recurrent_floats + wave * scratch_floats(K);
-    float *gbuf = xin + up4(K), *hbuf = gbuf + 3 * kMaxUnits, *st = hbuf + kMaxUnits;
+    float *rs = xin + up4(K);
     const int row0 = (blockIdx.x * kWavesPerWg + wave) * rows_per_wave;
     for (int i = 0; i < rows_per_wave; i++) {
         const int row = row0 + i;
         if (row >= B) break;                       // wave-uniform
         for (int k = lane; k < up4(K); k += kWave) xin[k] = k < K ? x[(size_t)row * K + k] : 0.f;
-        if (lane >= S && lane < up4(S)) st[lane] = 0.f;
-        lds_sync();
-        const bool dyn = branch[row] != 0;
-        float reward = 0.f;
-        float v[1];
-        if (dyn) {
-            v[0] = lstm_trunk(lds, d, T_DYN_RW, xin, K, S, gbuf, hbuf, lane);
-            reward = decode_lanes<1>(v, 0, S, lane);
-            v[0] = lstm_trunk(lds, d, T_DYN_ST, xin, K, S, gbuf, hbuf, lane);
-        } else {
-            v[0] = lstm_trunk(lds, d, T_ADY_ST, xin, K, S, gbuf, hbuf, lane);
-        }
-        scale_lanes<1>(v, 0, S, lane, st, hidden_out + (size_t)row * S);
-        lds_sync();
-        v[0] = lstm_trunk(lds, d, dyn ? T_PRE_POL : T_APR_POL, st, S, A, gbuf, hbuf, lane);
-        softmax_lanes<1>(v, A, lane, policy_out + (size_t)row * A);
-        v[0] = lstm_trunk(lds, d, dyn ? T_PRE_VAL : T_APR_VAL, st, S, S, gbuf, hbuf, lane);
-        const float value = decode_lanes<1>(v, 0, S, lane);
+        float reward, value;
+        recurrent_row(lds, d, xin, rs, branch[row] != 0, lane, hidden_out + (size_t)row * S, policy_out + (size_t)row * A, reward,
+                      value);
         if (lane == 0) {
             if (reward_out) reward_out[row] = reward;
             value_out[row] = value;
@@ -181,16 +93,6 @@ int allow_lds(Kern kern, size_t bytes) {
     return SMZ_OK;
 }
 
-int lstm_check(const smz_lstm_desc *d, const void *w) {
-    if (!d || !w) return SMZ_ERR_INVALID;
-    smz_lstm_desc t = *d;
-    if (smz_lstm_layout(&t) != SMZ_OK || t.total_floats != d->total_floats || t.recurrent_floats != d->recurrent_floats)
-        return SMZ_ERR_INVALID;
-    for (int i = 0; i < SMZ_LSTM_OFFSETS; i++)
-        if (t.off[i] != d->off[i]) return SMZ_ERR_INVALID;
-    return SMZ_OK;
-}
-
 void lstm_geometry(int B, int &blocks, int &rows_per_wave) {
     // two workgroups per CU (256 CUs); rows spread evenly over them
     const int waves = 512 * kWavesPerWg;
@@ -236,7 +138,7 @@ int smz_lstm_layout(smz_lstm_desc *d) {
 
 int smz_lstm_initial(const smz_lstm_desc *d, const float *weights_dev, const float *obs_dev, float *hidden_out_dev,
                      float *policy_out_dev, int B, smz_stream stream) {
-    if (lstm_check(d, weights_dev) != SMZ_OK || !obs_dev || !hidden_out_dev || !policy_out_dev || B < 1) return SMZ_ERR_INVALID;
+    if (desc_check(d, weights_dev) != SMZ_OK || !obs_dev || !hidden_out_dev || !policy_out_dev || B < 1) return SMZ_ERR_INVALID;
     int blocks, rpw;
     lstm_geometry(B, blocks, rpw);
     const size_t lds = (size_t)kWavesPerWg * scratch_floats(d->obs) * sizeof(float);
@@ -249,7 +151,7 @@ int smz_lstm_initial(const smz_lstm_desc *d, const float *weights_dev, const flo
 int smz_lstm_recurrent(const smz_lstm_desc *d, const float *weights_dev, const float *mlp_input_dev,
                        const uint8_t *branch_dev, float *hidden_out_dev, float *reward_out_dev, float *policy_out_dev,
                        float *value_out_dev, int B, smz_stream stream) {
-    if (lstm_check(d, weights_dev) != SMZ_OK || !mlp_input_dev || !branch_dev || !hidden_out_dev || !policy_out_dev ||
+    if (desc_check(d, weights_dev) != SMZ_OK || !mlp_input_dev || !branch_dev || !hidden_out_dev || !policy_out_dev ||
         !value_out_dev || B < 1)
         return SMZ_ERR_INVALID;
     int blocks, rpw;

@@ -34,7 +34,7 @@ class SearchEngine:
                  pb_c_base=19652, pb_c_init=1.25, discount=0.95, root_dirichlet_alpha=0.25,
                  root_exploration_fraction=0.25, device=None, rng_mode=_lib.RNG_MT19937_NUMPY, large_actions=False):
         """large_actions: create through smz_create_large_actions -- up to MAX_ACTIONS_LARGE actions, one wavefront per tree
-        (step-wise calls only: search_mlp / search_vision refuse such an engine)."""
+        (step-wise calls only: search_mlp / search_vision / search_lstm refuse such an engine)."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("SearchEngine needs a HIP device (torch.cuda.is_available() is False); "
@@ -269,6 +269,25 @@ class SearchEngine:
                                                   int(bool(train)), T, None if tab is None else tab.ctypes.data_as(C.c_void_p),
                                                   _ptr(self.action), _ptr(self.policy), _ptr(self.child_visits),
                                                   _ptr(self.root_value), self._stream()))
+        self._act_done = T
+
+    def search_lstm(self, lstm_desc, weights, hidden0, policy0, train=True, act_temperature=None):
+        """Whole search in one launch for `lstm_model` heads (smz_search_lstm): hidden0 [B,S] / policy0 [B,A] are
+        smz_lstm_initial's outputs.  `act_temperature` as in search_mlp."""
+        hidden0 = self._f32(hidden0.reshape(self.B, -1), (self.B, self.S))
+        policy0 = self._f32(policy0, (self.B, self.A))
+        self._act_done = None
+        self.env_stepped = False
+        if act_temperature is None:
+            _lib.check(self.lib.smz_search_lstm(self.h, C.byref(lstm_desc), _ptr(weights), _ptr(hidden0), _ptr(policy0),
+                                                int(bool(train)), self._stream()))
+            return
+        T = float(act_temperature)
+        tab = self._pow_table(T)
+        _lib.check(self.lib.smz_search_lstm_act(self.h, C.byref(lstm_desc), _ptr(weights), _ptr(hidden0), _ptr(policy0),
+                                                int(bool(train)), T, None if tab is None else tab.ctypes.data_as(C.c_void_p),
+                                                _ptr(self.action), _ptr(self.policy), _ptr(self.child_visits),
+                                                _ptr(self.root_value), self._stream()))
         self._act_done = T
 
     def root_stats(self):

@@ -132,7 +132,7 @@ class BatchedMCTS(_Hyper):
     def __init__(self, num_trees, pb_c_base=19652, pb_c_init=1.25, discount=0.95, root_dirichlet_alpha=0.25,
                  root_exploration_fraction=0.25, num_simulations=10, maxium_action_sample=2, number_of_player=1,
                  custom_loop=None, device=None, use_graph=True, fused=True, single_launch=True,
-                 rng_mode=_lib.RNG_MT19937_NUMPY):
+                 rng_mode=_lib.RNG_MT19937_NUMPY, lstm_single_launch=False):
         self._set_hyper(pb_c_base, pb_c_init, discount, root_dirichlet_alpha, root_exploration_fraction,
                         num_simulations, maxium_action_sample, number_of_player, custom_loop)
         self.num_trees = int(num_trees)
@@ -145,6 +145,9 @@ class BatchedMCTS(_Hyper):
         # would draw other numbers (shard invariance, tests/test_gpu_multirank.py, holds within one mode)
         self.rng_mode = resolve_rng_mode(rng_mode, self.num_trees)
         self.use_graph, self.fused, self.single_launch = bool(use_graph), bool(fused), bool(single_launch)
+        # lstm_model heads (HipLstmHeads) search step-wise unless this is set: then smz_lstm_initial + ONE smz_search_lstm launch
+        # (opt-in until its rate is known on more shapes; both paths give the same search, bit for bit)
+        self.lstm_single_launch = bool(lstm_single_launch)
         self.engine = None
         self._to_play = None
         self._graph = None
@@ -304,6 +307,24 @@ class BatchedMCTS(_Hyper):
                     raise
                 self._single = False
                 warnings.warn("single-launch vision search is outside its limits for this configuration "
+                              f"({err}): using the step-wise kernels")
+        # lstm_model heads, opt-in: representation + root policy (its own launch), then the whole search in one launch
+        if (self.single_launch and self.lstm_single_launch and isinstance(getattr(heads, "desc", None), _lib.LstmDesc)
+                and self._single is not False and self.num_trees <= self.single_launch_max_trees):
+            hidden, policy = heads.initial(observations)
+            eng = self._ensure_engine(policy.shape[1], hidden.shape[1])
+            if getattr(self, "_pending_seed", None) is not None:
+                eng.seed(self._pending_seed)
+                self._pending_seed = None
+            try:
+                eng.search_lstm(heads.desc, heads.weights, hidden, policy, train=train, act_temperature=act_temperature)
+                self._single = True
+                return eng
+            except _lib.SmzError as err:
+                if err.code != _lib.SMZ_ERR_TOO_LARGE or self._single is True:
+                    raise
+                self._single = False
+                warnings.warn("single-launch lstm search is outside its limits for this configuration "
                               f"({err}): using the step-wise kernels")
         return self._run_stepwise(observations, heads, train)
 

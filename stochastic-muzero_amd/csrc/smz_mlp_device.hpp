@@ -493,7 +493,8 @@ __device__ inline void dynamics_tail_pair(float a0, float a1, bool d0, bool d1, 
     const bool hi = lane >= 32, dyn = hi ? d1 : d0;
     const int j = lane & 31, oq = 32 + j, half = S / 2;
     const bool plog = dyn && j < S;                                                         // (S <= 32: the reward logits lie in P)
-    const bool pst = dyn ? j >= S : j < S, qst = dyn && oq < 2 * S;
+    // (dynamics: the state is outputs [S, 2 S) -- for S < 16 it ends inside P, the lanes behind it hold no output)
+    const bool pst = dyn ? (j >= S && j < 2 * S) : j < S, qst = dyn && oq < 2 * S;
     float mr = plog ? P : -__builtin_inff();
     float mn = op_min(pst ? P : __builtin_inff(), qst ? Q : __builtin_inff());
     float mx = op_max(pst ? P : -__builtin_inff(), qst ? Q : -__builtin_inff());

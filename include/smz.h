@@ -93,7 +93,7 @@ int smz_create(const smz_config *cfg, smz_handle **out);
 /* [sync] The same handle for 1 <= num_actions <= SMZ_MAX_ACTIONS_LARGE (SMZ_ERR_INVALID outside): the step-wise calls
  * (smz_root_init, smz_select, smz_expand_backup(_select), smz_act) run kernels with one wavefront per tree and the A-wide
  * arrays in LDS; results, tree layout and random-word consumption are those of an smz_create handle.  The single-launch
- * searches (smz_search_mlp*, smz_search_vision*, smz_search_lstm*) and smz_enable_stats return SMZ_ERR_TOO_LARGE on such a handle.  Path
+ * searches (smz_search_mlp*, smz_search_vision*, smz_search_lstm*, smz_search_mlp_wide*) and smz_enable_stats return SMZ_ERR_TOO_LARGE on such a handle.  Path
  * records name a child as (block << 10 | slot) instead of (block << 8 | slot); smz_debug_dump_tree decodes either. */
 int smz_create_large_actions(const smz_config *cfg, smz_handle **out);
 /* [sync] */
@@ -143,7 +143,7 @@ int smz_set_active(smz_handle *h, const uint8_t *active_dev);
  * at depth d plays cycle index (root + 2 (d >> 2) + ((d & 3) != 0)) mod n_cycle; the backup adds -value instead of value to
  * the value_sum of every node whose cycle VALUE differs from the root's.  Selection, the random draws and the value chain
  * are unchanged.  n_cycle > 1 selects the multi-player step-wise kernels (smz_expand_backup / smz_expand_backup_select);
- * the single-launch searches (smz_search_mlp*, smz_search_vision*, smz_search_lstm*) then fail with SMZ_ERR_INVALID.  n_cycle = 1 restores
+ * the single-launch searches (smz_search_mlp*, smz_search_vision*, smz_search_lstm*, smz_search_mlp_wide*) then fail with SMZ_ERR_INVALID.  n_cycle = 1 restores
  * the single-player search (cycle_values_host may then be NULL). */
 int smz_set_players(smz_handle *h, int n_cycle, const float *cycle_values_host, const int32_t *root_player_dev);
 /* Large batches: the row moves of a simulation round can be left to the network kernel.  When ids_dev is set, every
@@ -427,6 +427,27 @@ int smz_search_lstm_act(smz_handle *h, const smz_lstm_desc *desc, const float *w
                         const float *policy0_dev, int train, double temperature, const double *pow_table_host,
                         int32_t *action_dev, double *policy_dev, double *child_visits_dev, float *root_value_dev,
                         smz_stream stream);
+
+/* The same for the wide `mlp_model` shapes (a descriptor of smz_mlp_layout_wide: H <= 128, 2 S <= 128, A + S <= 128, weights too
+ * large for a CU's LDS; opt-in: BatchedMCTS(wide_single_launch=True)).  The root's hidden state and policy come from the heads'
+ * root evaluation (hidden0_dev [B,S], policy0_dev [B,A]), which stays its own launch.  A workgroup of 4 wavefronts owns
+ * 4 x ceil(B / 2048) trees for the whole search: one tree per lane in the tree phases; once per round the workgroup lists its
+ * leaves per branch in LDS and deals the <= 16-leaf tiles round-robin to its wavefronts, each tile through the tile body of
+ * smz_mlp_recurrent_wide (same device function, same compiler flags, weights streamed from L2: bit-identical to the step-wise
+ * calls).  Network inputs are read from the parent's hidden row, the new row is written into the new node's row; trees, hidden
+ * rows and path records stay in global memory in the handle's layout, results are read as after the step-wise calls.  desc->A
+ * and desc->S must be the handle's (SMZ_ERR_INVALID otherwise, as for a descriptor smz_mlp_layout_wide would not produce, a null
+ * argument or a multi-player handle).  SMZ_ERR_TOO_LARGE outside the kernel's limits (exactly 2 or 4 actions, at most 64 trees
+ * per wavefront, LDS map <= 160 KB) and on a large-action handle: use the step-wise entry points then.  MT19937 and Philox
+ * handles alike; smz_set_active is honoured; legal under stream capture.  The environment variable SMZ_WIDE_SEARCH_TPW (>= 1)
+ * replaces the trees per wavefront (the results do not depend on it).  monte_carlo_tree_search.py:311-349. */
+int smz_search_mlp_wide(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *hidden0_dev,
+                        const float *policy0_dev, int train, smz_stream stream);
+/* ... followed by smz_act in the tail of the same launch (as smz_search_mlp_act). */
+int smz_search_mlp_wide_act(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *hidden0_dev,
+                            const float *policy0_dev, int train, double temperature, const double *pow_table_host,
+                            int32_t *action_dev, double *policy_dev, double *child_visits_dev, float *root_value_dev,
+                            smz_stream stream);
 
 /* smz_mlp_recurrent on rows that live in a handle's hidden-state storage (smz_get_hidden_layout): leaf i's network input
  * is the hidden row of node ids_dev[2i+1] of tree i plus the one-hot of last_action_dev[i], its new hidden row is written

@@ -55,6 +55,8 @@ def mcts_kwargs(config, num_simulations=None):
               custom_loop=m["custom_loop"])
     if "lstm_single_launch" in m:       # (not a key of the reference's configs) lstm_model searches in one launch: BatchedMCTS
         kw["lstm_single_launch"] = bool(m["lstm_single_launch"])
+    if "wide_single_launch" in m:       # (not a key of the reference's configs) wide mlp_model searches in one launch: BatchedMCTS
+        kw["wide_single_launch"] = bool(m["wide_single_launch"])
     return kw
 
 

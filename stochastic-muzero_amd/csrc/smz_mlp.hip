@@ -13,6 +13,7 @@
 
 #include "../../include/smz.h"
 #include "smz_mlp_device.hpp"
+#include "smz_mlp_wide_device.hpp"
 
 using namespace smz_mlp;
 
@@ -96,7 +97,6 @@ __global__ void __launch_bounds__(512) k_mlp_initial(smz_mlp_desc d, const float
 // The tails work on the MFMA output layout (lane = (neuron group g, leaf j), registers = neurons 16t + 4g + r of the four
 // 16-neuron tiles t): sums in the association of smz_mlp::wave_sum -- registers, lanes ^ 16, ^ 32, then tiles.
 // Bit-identical to k_mlp_recurrent (tests/test_gpu_mlp_heads.py).
-typedef float v4f __attribute__((ext_vector_type(4)));
 #ifndef SMZ_MFMA_COMPACT
 #define SMZ_MFMA_COMPACT 1         // 0: round 5's launch -- the 64-wide LDS weight image (100 KB) and twelve wavefronts
 #endif
@@ -107,19 +107,10 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 // tile (MFMAs, then tails on their results): the matrix pipe was busy 32 % of the launch with three chains per SIMD
 // (profiles/r06_d_pmc_262k.json); and 32 tiles per CU at 131 072 leaves split 2 + 2 over sixteen wavefronts instead of 3 + 3 + 2.
 constexpr bool kMfmaCompact = SMZ_MFMA_COMPACT != 0;
-constexpr int kTileLeaves = 16, kMfmaWaves = kMfmaCompact ? 16 : 12;
+constexpr int kMfmaWaves = kMfmaCompact ? 16 : 12;   // (kTileLeaves = 16: smz_mlp_wide_device.hpp)
 constexpr int kTileFloats = 32 * 32;                 // one activation tile per wavefront: [32 input pairs][16 leaves][2]
 
-__device__ inline float lane_xor16(float v) {
-    const unsigned u = __float_as_uint(v);
-    const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    return __uint_as_float(((threadIdx.x & 16) ? r[0] : r[1]));
-}
-__device__ inline float lane_xor32(float v) {
-    const unsigned u = __float_as_uint(v);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    return __uint_as_float(((threadIdx.x & 32) ? r[0] : r[1]));
-}
+// (lane_xor16 / lane_xor32, tile_max / tile_min: smz_mlp_wide_device.hpp)
 // sum over the 64 output positions o = 16 t + 4 g + r of a leaf, a[t][r] = the lane's values (zeros for non-members)
 __device__ inline float tile_sum(const float (&a)[4][4]) {
     float s[4];
@@ -131,8 +122,6 @@ __device__ inline float tile_sum(const float (&a)[4][4]) {
     for (int t = 0; t < 4; t++) s[t] = s[t] + lane_xor32(s[t]);
     return (s[0] + s[1]) + (s[2] + s[3]);
 }
-__device__ inline float tile_max(float m) { m = fmaxf(m, lane_xor16(m)); return fmaxf(m, lane_xor32(m)); }
-__device__ inline float tile_min(float m) { m = fminf(m, lane_xor16(m)); return fminf(m, lane_xor32(m)); }
 
 // y[t][r] = bias[16t + 4g + r] + sum_k W[k][16t + 4g + r] * x[k][leaf j]: K8 groups of eight inputs, W = LDS weight image
 // (4-way interleaved, 64 outputs wide), xp = activation tile [input pair][leaf][2]
@@ -422,52 +411,11 @@ __global__ void __launch_bounds__(kMfmaWaves *kWave) k_mlp_recurrent_mfma(smz_ml
 }
 
 // -------------------------------------------------------------------------------------------------------------------
-// Networks too wide for LDS residency (the reference's config/experiment_434_config.json: state_space_dimensions 61,
-// hidden_layer_dimensions 126, and its checkpoint 450 with number_of_hidden_layer 4; any shape with H <= 128, 2 S <= 128,
-// A + S <= 128 -- hidden layers are the same Linear(H, H) applied L times, neural_network_mlp_model.py:122-142): the same
-// 16-leaf tiles with the weights streamed from L2 -- A operands as 8-byte global loads of a 128-wide packed image
-// (smz_mlp_layout_wide), prefetched one input group ahead of the MFMAs that consume them; layers are 8 tiles of 16
-// neurons, dimensions are run-time values.  Outputs agree with the torch-GEMM heads / the reference's tapes within the
-// measured float tolerances (no bit-identity partner exists for these shapes).
-constexpr int kWideOP = 128, kWideTiles = 8, kWideWaves = 8;
-constexpr int kWideTileFloats = 64 * 32;              // [64 input pairs][16 leaves][2]
-
-__device__ inline void wide_layer(const float *__restrict__ W, const float *__restrict__ bias, const float *xp, int K8, int lane, v4f (&y)[kWideTiles]) {
-    const int g = lane >> 4, j = lane & 15;
-    v4f o[kWideTiles];                                      // y = the even-input accumulators (from the bias), o = the odd ones
-    float2 wa[3][kWideTiles];                               // weights of three consecutive input groups: two in flight ahead
-    const float *Wl = W + ((size_t)(g >> 1) * kWideOP + j) * 4 + 2 * (g & 1);
-    auto wload = [&](int slot, int c) {
-#pragma unroll
-        for (int t = 0; t < kWideTiles; t++) wa[slot][t] = *reinterpret_cast<const float2 *>(Wl + ((size_t)2 * c * kWideOP + 16 * t) * 4);
-    };
-#pragma unroll
-    for (int t = 0; t < kWideTiles; t++) {
-        const float4 b = *reinterpret_cast<const float4 *>(bias + 16 * t + 4 * g);
-        y[t] = v4f{b.x, b.y, b.z, b.w};
-        o[t] = v4f{0.f, 0.f, 0.f, 0.f};
-    }
-    wload(0, 0);
-    if (K8 > 1) wload(1, 1);
-    for (int c = 0; c < K8; c += 3) {                       // three input groups per trip: static indices into wa[]
-#pragma unroll
-        for (int h = 0; h < 3; h++) {
-            const int cc = c + h;
-            if (cc < K8) {                                  // wave-uniform
-                const float2 xb = *reinterpret_cast<const float2 *>(xp + ((4 * cc + g) * kTileLeaves + j) * 2);
-                if (cc + 2 < K8) wload((h + 2) % 3, cc + 2);
-#pragma unroll
-                for (int t = 0; t < kWideTiles; t++) {
-                    y[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[h][t].x, xb.x, y[t], 0, 0, 0);
-                    o[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[h][t].y, xb.y, o[t], 0, 0, 0);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < kWideTiles; t++) y[t] = y[t] + o[t];
-}
-__device__ inline float wide_sum(float s) { s = s + lane_xor16(s); return s + lane_xor32(s); }
+// Networks too wide for LDS residency (H <= 128, 2 S <= 128, A + S <= 128): the 16-leaf tiles of smz_mlp_wide_device.hpp
+// (wide_tile: one tile of one branch by one wavefront, weights streamed from L2), shared with the whole-search kernel
+// k_search_mlp_wide.  Outputs agree with the torch-GEMM heads / the reference's tapes within the measured float tolerances
+// (no bit-identity partner exists for these shapes among the head kernels).
+constexpr int kWideWaves = 8;
 
 __global__ void __launch_bounds__(kWideWaves *kWave) k_mlp_recurrent_wide(smz_mlp_desc d, const float *__restrict__ weights,
                                                                           const float *__restrict__ x, const uint8_t *__restrict__ branch,
@@ -475,10 +423,8 @@ __global__ void __launch_bounds__(kWideWaves *kWave) k_mlp_recurrent_wide(smz_ml
                                                                           float *__restrict__ policy_out, float *__restrict__ value_out,
                                                                           int B, int chunk) {
     float *lds = reinterpret_cast<float *>(smz_mlp_lds4);
-    const int S = d.S, A = d.A, H = d.H, half = S / 2, XW = S + A;
-    const int K8x = (XW + 7) >> 3, K8h = (H + 7) >> 3, K8s = (S + 7) >> 3;
+    const int S = d.S, A = d.A, XW = S + A;
     const int lane = threadIdx.x & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    const int g = lane >> 4, j = lane & 15;
     const int waves = blockDim.x / kWave;                 // 2 .. kWideWaves: small batches spread their tiles over more workgroups
     float *tile = lds + wave * kWideTileFloats;
     unsigned short *list = reinterpret_cast<unsigned short *>(lds + waves * kWideTileFloats);   // [2][kMaxChunk]
@@ -497,135 +443,13 @@ __global__ void __launch_bounds__(kWideWaves *kWave) k_mlp_recurrent_wide(smz_ml
             const bool ady = tl >= t0;                                       // wave-uniform
             const int tt = ady ? tl - t0 : tl, count = (ady ? n1 : n0) - tt * kTileLeaves;
             const unsigned short *li = list + (ady ? kMaxChunk : 0) + tt * kTileLeaves;
-            const bool mine = j < count;
-            const int row = base + li[mine ? j : 0];
-            // network inputs [hidden | one-hot] -> tile, zero beyond them up to the layer's 8-input groups
-            for (int i = lane; i < kTileLeaves * 8 * K8x; i += kWave) {
-                const int lf = i / (8 * K8x), k = i % (8 * K8x);
-                const int rr = base + li[lf < count ? lf : 0];
-                tile[((k >> 1) * kTileLeaves + lf) * 2 + (k & 1)] = k < XW ? x[(size_t)rr * XW + k] : 0.f;
-            }
-            lds_sync();
-            // (selects between constant-index descriptor entries: a run-time index would put the table in scratch)
-            const int w_in = ady ? d.off[M_ADY_IN] : d.off[M_DYN_IN], b_in = ady ? d.off[M_COUNT + M_ADY_IN] : d.off[M_COUNT + M_DYN_IN];
-            const int w_out = ady ? d.off[M_ADY_OUT] : d.off[M_DYN_OUT], b_out = ady ? d.off[M_COUNT + M_ADY_OUT] : d.off[M_COUNT + M_DYN_OUT];
-            const int wp_in = ady ? d.off[M_APR_IN] : d.off[M_PRE_IN], bp_in = ady ? d.off[M_COUNT + M_APR_IN] : d.off[M_COUNT + M_PRE_IN];
-            const int wp_out = ady ? d.off[M_APR_OUT] : d.off[M_PRE_OUT], bp_out = ady ? d.off[M_COUNT + M_APR_OUT] : d.off[M_COUNT + M_PRE_OUT];
-            const int w_mid = ady ? d.off[M_ADY_MID] : d.off[M_DYN_MID], b_mid = ady ? d.off[M_COUNT + M_ADY_MID] : d.off[M_COUNT + M_DYN_MID];
-            const int wp_mid = ady ? d.off[M_APR_MID] : d.off[M_PRE_MID], bp_mid = ady ? d.off[M_COUNT + M_APR_MID] : d.off[M_COUNT + M_PRE_MID];
-            v4f y[kWideTiles];
-            auto trunk_store = [&]() {
-#pragma unroll
-                for (int t = 0; t < kWideTiles; t++) {
-                    const int nn = 16 * t + 4 * g;
-                    *reinterpret_cast<float2 *>(tile + (((nn >> 1) + 0) * kTileLeaves + j) * 2) = make_float2(elu(y[t][0]), elu(y[t][1]));
-                    *reinterpret_cast<float2 *>(tile + (((nn >> 1) + 1) * kTileLeaves + j) * 2) = make_float2(elu(y[t][2]), elu(y[t][3]));
-                }
-            };
-            wide_layer(weights + w_in, weights + b_in, tile, K8x, lane, y);
-            lds_sync();
-            trunk_store();
-            lds_sync();
-            for (int l = 0; l < d.L; l++) {          // the SAME Linear(H, H) + ELU applied L times (neural_network_mlp_model.py:122-142)
-                wide_layer(weights + w_mid, weights + b_mid, tile, K8h, lane, y);
-                lds_sync();
-                trunk_store();
-                lds_sync();
-            }
-            wide_layer(weights + w_out, weights + b_out, tile, K8h, lane, y);
-            float reward = 0.f;
-            {   // dynamics: [reward logits 0..S-1 | next state S..2S-1]; afterstate dynamics: next state 0..S-1
-                const int lo = ady ? 0 : S;
-                float mr = -__builtin_inff(), mn = __builtin_inff(), mx = -__builtin_inff();
-#pragma unroll
-                for (int t = 0; t < kWideTiles; t++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int o = 16 * t + 4 * g + r;
-                        if (!ady && o < S) mr = fmaxf(mr, y[t][r]);
-                        if (o >= lo && o < lo + S) { mn = fminf(mn, y[t][r]); mx = fmaxf(mx, y[t][r]); }
-                    }
-                mn = tile_min(mn); mx = tile_max(mx);
-                if (!ady) {
-                    mr = tile_max(mr);
-                    float den = 0.f, num = 0.f;
-#pragma unroll
-                    for (int t = 0; t < kWideTiles; t++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            const int o = 16 * t + 4 * g + r;
-                            if (o < S) { const float ev = smz_exp(y[t][r] - mr); den += ev; num += (float)(o - half) * ev; }
-                        }
-                    reward = support_to_scalar(wide_sum(num), wide_sum(den));
-                }
-                float sc = mx - mn;
-                if (sc < 1e-5f) sc += 1e-5f;
-                lds_sync();
-#pragma unroll
-                for (int t = 0; t < kWideTiles; t++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int o = 16 * t + 4 * g + r, k = o - lo;
-                        if (k >= 0 && k < S) {
-                            const float hv = __fdividef(y[t][r] - mn, sc);
-                            tile[((k >> 1) * kTileLeaves + j) * 2 + (k & 1)] = hv;
-                            if (mine) hidden_out[(size_t)row * S + k] = hv;
-                        }
-                    }
-                for (int i = lane; i < kTileLeaves * (8 * K8s - S); i += kWave) {          // zero inputs S .. 8 K8s - 1
-                    const int lf = i / (8 * K8s - S), k = S + i % (8 * K8s - S);
-                    tile[((k >> 1) * kTileLeaves + lf) * 2 + (k & 1)] = 0.f;
-                }
-            }
-            lds_sync();
-            wide_layer(weights + wp_in, weights + bp_in, tile, K8s, lane, y);
-            lds_sync();
-            trunk_store();
-            lds_sync();
-            for (int l = 0; l < d.L; l++) {
-                wide_layer(weights + wp_mid, weights + bp_mid, tile, K8h, lane, y);
-                lds_sync();
-                trunk_store();
-                lds_sync();
-            }
-            wide_layer(weights + wp_out, weights + bp_out, tile, K8h, lane, y);
-            {   // [policy logits 0..A-1 | value logits A..A+S-1]
-                float mp = -__builtin_inff(), mv = -__builtin_inff();
-#pragma unroll
-                for (int t = 0; t < kWideTiles; t++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int o = 16 * t + 4 * g + r;
-                        if (o < A) mp = fmaxf(mp, y[t][r]);
-                        else if (o < A + S) mv = fmaxf(mv, y[t][r]);
-                    }
-                mp = tile_max(mp); mv = tile_max(mv);
-                float dp = 0.f, dv = 0.f, nv = 0.f;
-#pragma unroll
-                for (int t = 0; t < kWideTiles; t++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int o = 16 * t + 4 * g + r;
-                        if (o < A) { y[t][r] = smz_exp(y[t][r] - mp); dp += y[t][r]; }
-                        else if (o < A + S) { const float ev = smz_exp(y[t][r] - mv); dv += ev; nv += (float)(o - A - half) * ev; }
-                    }
-                dp = wide_sum(dp);
-                const float value = support_to_scalar(wide_sum(nv), wide_sum(dv));
-                if (mine) {
-#pragma unroll
-                    for (int t = 0; t < kWideTiles; t++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            const int o = 16 * t + 4 * g + r;
-                            if (o < A) policy_out[(size_t)row * A + o] = __fdividef(y[t][r], dp);
-                        }
-                    if (g == 0) {
-                        value_out[row] = value;
-                        if (reward_out) reward_out[row] = reward;
-                    }
-                }
-            }
-            lds_sync();
+            wide_tile(d, weights, tile, count, ady, lane,
+                      [&](int lf, int k) { return x[(size_t)(base + li[lf]) * XW + k]; },
+                      [&](int lf) {
+                          const int row = base + li[lf];
+                          return WideDst{hidden_out + (size_t)row * S, policy_out + (size_t)row * A, value_out + row,
+                                         reward_out ? reward_out + row : nullptr};
+                      });
         }
         __syncthreads();
     }

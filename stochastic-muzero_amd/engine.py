@@ -290,6 +290,25 @@ class SearchEngine:
                                                 _ptr(self.root_value), self._stream()))
         self._act_done = T
 
+    def search_mlp_wide(self, wide_desc, packed, hidden0, policy0, train=True, act_temperature=None):
+        """Whole search in one launch for the wide `mlp_model` heads (smz_search_mlp_wide; HipMlpTileHeads.wide_desc / .packed):
+        hidden0 [B,S] / policy0 [B,A] are the outputs of the heads' initial().  `act_temperature` as in search_mlp."""
+        hidden0 = self._f32(hidden0.reshape(self.B, -1), (self.B, self.S))
+        policy0 = self._f32(policy0, (self.B, self.A))
+        self._act_done = None
+        self.env_stepped = False
+        if act_temperature is None:
+            _lib.check(self.lib.smz_search_mlp_wide(self.h, C.byref(wide_desc), _ptr(packed), _ptr(hidden0), _ptr(policy0),
+                                                    int(bool(train)), self._stream()))
+            return
+        T = float(act_temperature)
+        tab = self._pow_table(T)
+        _lib.check(self.lib.smz_search_mlp_wide_act(self.h, C.byref(wide_desc), _ptr(packed), _ptr(hidden0), _ptr(policy0),
+                                                    int(bool(train)), T, None if tab is None else tab.ctypes.data_as(C.c_void_p),
+                                                    _ptr(self.action), _ptr(self.policy), _ptr(self.child_visits),
+                                                    _ptr(self.root_value), self._stream()))
+        self._act_done = T
+
     def root_stats(self):
         _lib.check(self.lib.smz_root_stats(self.h, _ptr(self.visits), _ptr(self.priors), _ptr(self.root_value),
                                            _ptr(self.child_reward), self._stream()))

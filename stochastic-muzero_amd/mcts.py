@@ -132,7 +132,7 @@ class BatchedMCTS(_Hyper):
     def __init__(self, num_trees, pb_c_base=19652, pb_c_init=1.25, discount=0.95, root_dirichlet_alpha=0.25,
                  root_exploration_fraction=0.25, num_simulations=10, maxium_action_sample=2, number_of_player=1,
                  custom_loop=None, device=None, use_graph=True, fused=True, single_launch=True,
-                 rng_mode=_lib.RNG_MT19937_NUMPY, lstm_single_launch=False):
+                 rng_mode=_lib.RNG_MT19937_NUMPY, lstm_single_launch=False, wide_single_launch=False):
         self._set_hyper(pb_c_base, pb_c_init, discount, root_dirichlet_alpha, root_exploration_fraction,
                         num_simulations, maxium_action_sample, number_of_player, custom_loop)
         self.num_trees = int(num_trees)
@@ -148,6 +148,9 @@ class BatchedMCTS(_Hyper):
         # lstm_model heads (HipLstmHeads) search step-wise unless this is set: then smz_lstm_initial + ONE smz_search_lstm launch
         # (opt-in until its rate is known on more shapes; both paths give the same search, bit for bit)
         self.lstm_single_launch = bool(lstm_single_launch)
+        # wide mlp_model heads (HipMlpTileHeads) search step-wise unless this is set: then heads.initial + ONE smz_search_mlp_wide
+        # launch (opt-in: its rate against the step-wise graph is in DESIGN.md 3.6; both paths give the same search, bit for bit)
+        self.wide_single_launch = bool(wide_single_launch)
         self.engine = None
         self._to_play = None
         self._graph = None
@@ -325,6 +328,24 @@ class BatchedMCTS(_Hyper):
                     raise
                 self._single = False
                 warnings.warn("single-launch lstm search is outside its limits for this configuration "
+                              f"({err}): using the step-wise kernels")
+        # wide mlp_model heads, opt-in: root evaluation (torch GEMMs), then the whole search in one launch
+        if (self.single_launch and self.wide_single_launch and isinstance(getattr(heads, "wide_desc", None), _lib.MlpDesc)
+                and self._single is not False and self.num_trees <= self.single_launch_max_trees):
+            hidden, policy = heads.initial(observations)
+            eng = self._ensure_engine(policy.shape[1], hidden.shape[1])
+            if getattr(self, "_pending_seed", None) is not None:
+                eng.seed(self._pending_seed)
+                self._pending_seed = None
+            try:
+                eng.search_mlp_wide(heads.wide_desc, heads.packed, hidden, policy, train=train, act_temperature=act_temperature)
+                self._single = True
+                return eng
+            except _lib.SmzError as err:
+                if err.code != _lib.SMZ_ERR_TOO_LARGE or self._single is True:
+                    raise
+                self._single = False
+                warnings.warn("single-launch wide mlp search is outside its limits for this configuration "
                               f"({err}): using the step-wise kernels")
         return self._run_stepwise(observations, heads, train)
 

@@ -143,7 +143,8 @@ int smz_set_active(smz_handle *h, const uint8_t *active_dev);
  * at depth d plays cycle index (root + 2 (d >> 2) + ((d & 3) != 0)) mod n_cycle; the backup adds -value instead of value to
  * the value_sum of every node whose cycle VALUE differs from the root's.  Selection, the random draws and the value chain
  * are unchanged.  n_cycle > 1 selects the multi-player step-wise kernels (smz_expand_backup / smz_expand_backup_select);
- * the single-launch searches (smz_search_mlp*, smz_search_vision*, smz_search_lstm*, smz_search_mlp_wide*) then fail with SMZ_ERR_INVALID.  n_cycle = 1 restores
+ * the single-launch searches (smz_search_mlp*, smz_search_vision*, smz_search_lstm*, smz_search_mlp_wide*) then fail with SMZ_ERR_INVALID
+ * -- all but smz_search_mlp_players(_act), the single launch of exactly these handles.  n_cycle = 1 restores
  * the single-player search (cycle_values_host may then be NULL). */
 int smz_set_players(smz_handle *h, int n_cycle, const float *cycle_values_host, const int32_t *root_player_dev);
 /* Large batches: the row moves of a simulation round can be left to the network kernel.  When ids_dev is set, every
@@ -448,6 +449,26 @@ int smz_search_mlp_wide_act(smz_handle *h, const smz_mlp_desc *desc, const float
                             const float *policy0_dev, int train, double temperature, const double *pow_table_host,
                             int32_t *action_dev, double *policy_dev, double *child_visits_dev, float *root_value_dev,
                             smz_stream stream);
+
+/* smz_search_mlp for a MULTI-PLAYER handle (smz_set_players with n_cycle > 1; opt-in: BatchedMCTS(players_single_launch=True)):
+ * the whole search of every tree in one launch, with the signed backup of mcts:299-308.  Same arguments and the same networks as
+ * smz_search_mlp (a descriptor smz_mlp_layout accepts).  The kernel, k_search_mlp_players<MAXA, KS, PHX>, is the generic path of
+ * k_search_mlp -- trees in global memory, any action count up to 32 inside its bucket (7 or 9 actions of a board game), K = 2 or
+ * run-time K, MT19937 and Philox handles, smz_set_active honoured -- calling expand_backup_tree<..., MP> as the step-wise
+ * multi-player kernels do: trees, statistics and stream positions are bit-identical to theirs.  The root players are whatever the
+ * root_player_dev buffer of smz_set_players holds when the kernel runs (NULL: player 0).  A wavefront owns ceil(B / 2048) trees
+ * (workgroups of 8 wavefronts, one per CU); the environment variable SMZ_PLAYERS_SEARCH_TPW (>= 1) replaces that count (the results
+ * do not depend on it).
+ * SMZ_ERR_INVALID: a null argument, a one-player handle (use smz_search_mlp), a descriptor smz_mlp_layout would not produce,
+ * dimensions other than the handle's, statistics enabled (smz_enable_stats) or a SMZ_DEBUG_SKIP switch set (there is no
+ * instrumented variant).  SMZ_ERR_TOO_LARGE: a large-action handle, more than 64 trees per wavefront, an LDS map above 160 KB:
+ * use the step-wise entry points then.  Legal under stream capture.  monte_carlo_tree_search.py:311-349. */
+int smz_search_mlp_players(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, int train,
+                           smz_stream stream);
+/* ... followed by smz_act in the tail of the same launch (as smz_search_mlp_act). */
+int smz_search_mlp_players_act(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, int train,
+                               double temperature, const double *pow_table_host, int32_t *action_dev, double *policy_dev,
+                               double *child_visits_dev, float *root_value_dev, smz_stream stream);
 
 /* smz_mlp_recurrent on rows that live in a handle's hidden-state storage (smz_get_hidden_layout): leaf i's network input
  * is the hidden row of node ids_dev[2i+1] of tree i plus the one-hot of last_action_dev[i], its new hidden row is written

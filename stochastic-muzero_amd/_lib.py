@@ -122,6 +122,8 @@ SIGNATURES = {
     "smz_search_lstm_act": (C.c_int, [_P, C.POINTER(LstmDesc), _P, _P, _P, C.c_int, C.c_double, _P, _P, _P, _P, _P, _P]),
     "smz_search_mlp_wide": (C.c_int, [_P, C.POINTER(MlpDesc), _P, _P, _P, C.c_int, _P]),
     "smz_search_mlp_wide_act": (C.c_int, [_P, C.POINTER(MlpDesc), _P, _P, _P, C.c_int, C.c_double, _P, _P, _P, _P, _P, _P]),
+    "smz_search_mlp_players": (C.c_int, [_P, C.POINTER(MlpDesc), _P, _P, C.c_int, _P]),
+    "smz_search_mlp_players_act": (C.c_int, [_P, C.POINTER(MlpDesc), _P, _P, C.c_int, C.c_double, _P, _P, _P, _P, _P, _P]),
     "smz_cartpole_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P]),
     "smz_cartpole_step_pack": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P]),
     "smz_cartpole_step_ctl": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(EpisodeCtl), _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P]),

@@ -309,6 +309,25 @@ class SearchEngine:
                                                     _ptr(self.root_value), self._stream()))
         self._act_done = T
 
+    def search_mlp_players(self, mlp_desc, weights, obs, train=True, act_temperature=None):
+        """Whole search in one launch for a multi-player engine (set_players with more than one cycle entry) and LDS-resident
+        mlp_model heads (smz_search_mlp_players).  The root players are what `self.root_player` holds (set_root_player).
+        `act_temperature` as in search_mlp."""
+        assert obs.dtype == torch.float32 and obs.is_contiguous() and obs.shape[0] == self.B
+        self._act_done = None
+        self.env_stepped = False
+        if act_temperature is None:
+            _lib.check(self.lib.smz_search_mlp_players(self.h, C.byref(mlp_desc), _ptr(weights), _ptr(obs), int(bool(train)),
+                                                       self._stream()))
+            return
+        T = float(act_temperature)
+        tab = self._pow_table(T)
+        _lib.check(self.lib.smz_search_mlp_players_act(self.h, C.byref(mlp_desc), _ptr(weights), _ptr(obs), int(bool(train)), T,
+                                                       None if tab is None else tab.ctypes.data_as(C.c_void_p), _ptr(self.action),
+                                                       _ptr(self.policy), _ptr(self.child_visits), _ptr(self.root_value),
+                                                       self._stream()))
+        self._act_done = T
+
     def root_stats(self):
         _lib.check(self.lib.smz_root_stats(self.h, _ptr(self.visits), _ptr(self.priors), _ptr(self.root_value),
                                            _ptr(self.child_reward), self._stream()))

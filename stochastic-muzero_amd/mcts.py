@@ -132,7 +132,8 @@ class BatchedMCTS(_Hyper):
     def __init__(self, num_trees, pb_c_base=19652, pb_c_init=1.25, discount=0.95, root_dirichlet_alpha=0.25,
                  root_exploration_fraction=0.25, num_simulations=10, maxium_action_sample=2, number_of_player=1,
                  custom_loop=None, device=None, use_graph=True, fused=True, single_launch=True,
-                 rng_mode=_lib.RNG_MT19937_NUMPY, lstm_single_launch=False, wide_single_launch=False):
+                 rng_mode=_lib.RNG_MT19937_NUMPY, lstm_single_launch=False, wide_single_launch=False,
+                 players_single_launch=False):
         self._set_hyper(pb_c_base, pb_c_init, discount, root_dirichlet_alpha, root_exploration_fraction,
                         num_simulations, maxium_action_sample, number_of_player, custom_loop)
         self.num_trees = int(num_trees)
@@ -151,6 +152,10 @@ class BatchedMCTS(_Hyper):
         # wide mlp_model heads (HipMlpTileHeads) search step-wise unless this is set: then heads.initial + ONE smz_search_mlp_wide
         # launch (opt-in: its rate against the step-wise graph is in DESIGN.md 3.6; both paths give the same search, bit for bit)
         self.wide_single_launch = bool(wide_single_launch)
+        # multi-player searches (number_of_player > 1, custom_loop) with HipMlpHeads run step-wise unless this is set: then ONE
+        # smz_search_mlp_players launch (opt-in: its rate against the step-wise graph is in DESIGN.md 3.7; both paths give the same
+        # search, bit for bit)
+        self.players_single_launch = bool(players_single_launch)
         self.engine = None
         self._to_play = None
         self._graph = None
@@ -248,7 +253,8 @@ class BatchedMCTS(_Hyper):
         `to_play` (multi-player searches: number_of_player > 1 or a custom loop): int [B] root player index of every tree
         (Player_cycle.global_step() of the reference: the move number in the current game, mod the cycle length), a host
         array or a device tensor, copied into the engine's buffer on the current stream; None = 0 for every tree.  These
-        searches run on the step-wise kernels.
+        searches run on the step-wise kernels, or, with players_single_launch and HipMlpHeads, as ONE kernel launch
+        (smz_search_mlp_players) when that fits its limits -- the same search, bit for bit.
         With HipMlpHeads the whole search is ONE kernel launch (smz_search_mlp) when it fits in LDS; otherwise the
         step-wise kernels run, captured in a HIP graph unless use_graph is off.
         `env_step` (envs.CartPoleVec.fused_step): the single launch also steps the built-in env and appends the record;
@@ -267,7 +273,26 @@ class BatchedMCTS(_Hyper):
     def _run(self, observations, heads, train, act_temperature, env_step, record_obs):
         self._recorded = False
         if self.n_cycle > 1:
-            # the multi-player backup exists in the step-wise kernels only (the single launch refuses such a handle)
+            # the multi-player backup: the step-wise kernels, or (opt-in, HipMlpHeads) the single launch built for these handles;
+            # every other single launch refuses them
+            if (self.players_single_launch and self.single_launch and isinstance(getattr(heads, "desc", None), _lib.MlpDesc)
+                    and int(heads.A) <= _lib.MAX_ACTIONS and self.num_trees <= self.single_launch_max_trees
+                    and self._single is not False):
+                eng = self._ensure_engine(heads.A, heads.S)
+                if getattr(self, "_pending_seed", None) is not None:
+                    eng.seed(self._pending_seed)
+                    self._pending_seed = None
+                self._stage_to_play(eng)
+                try:
+                    eng.search_mlp_players(heads.desc, heads.weights, observations, train=train, act_temperature=act_temperature)
+                    self._single = True
+                    return eng
+                except _lib.SmzError as err:
+                    if err.code != _lib.SMZ_ERR_TOO_LARGE or self._single is True:
+                        raise
+                    self._single = False
+                    warnings.warn("single-launch multi-player search is outside its limits for this configuration "
+                                  f"({err}): using the step-wise kernels")
             return self._run_stepwise(observations, heads, train)
         if int(getattr(heads, "A", 0)) > _lib.MAX_ACTIONS:
             # more actions than the per-lane kernels take: the wave-per-tree step-wise kernels (no single launch)

@@ -923,15 +923,11 @@ __device__ inline uint32_t select_block_decide(const Params &P, int b, int depth
     const int c = pick ? k.chd[1] : k.chd[0];
     return 0x100u | ((uint32_t)pick << 7) | (uint32_t)c;
 }
-template <int MAXA, bool YV, class RNG, bool LF = false>
-__device__ inline uint32_t select_block(const Params &P, const uint32_t *tb, int b, int depth, int root_visit, float mn, float mx,
-                                        const uint32_t *stage, int used, int staged, const double *pbc_sqrt) {
-    static_assert(MAXA == 2, "one bit for the pick: the block-parallel selection is built for two actions");
-    if constexpr (LF && SMZ_SELECT_LOADS_FIRST) {
-        BlockRaw in;
-        select_block_request<MAXA, YV>(P, tb, b, in);
-        return select_block_decide<MAXA, YV, RNG>(P, b, depth, root_visit, mn, mx, stage, used, staged, pbc_sqrt, in);
-    }
+// (the block's children stay with the caller: the mask-based descent, SMZ_SELECT_MASKS, writes the path record of a block on
+//  the path from the registers of the lane that evaluated it; `k` is loaded only when the return value is not 0)
+template <int MAXA, bool YV, class RNG>
+__device__ inline uint32_t select_block_kids(const Params &P, const uint32_t *tb, int b, int depth, int root_visit, float mn, float mx,
+                                             const uint32_t *stage, int used, int staged, const double *pbc_sqrt, Kids<2> &k) {
     constexpr bool RY = YV && MAXA <= 8;
     const int A = P.A;
     const bool chance = depth_flag(depth) != 0;
@@ -948,7 +944,6 @@ __device__ inline uint32_t select_block(const Params &P, const uint32_t *tb, int
         const bool root = b == 0;
         const uint32_t *bp = root ? tb : tb + P.rb_words + (size_t)(b - 1) * P.eb_words;
         const uint32_t *aux = root ? tb + (RY ? P.ry_off : 0) : tb + P.thr_off + (size_t)(b - 1) * P.thr_stride;
-        Kids<2> k;
         load_kids_static<2>(bp, k);
         if (chance) {
             pick = (*reinterpret_cast<const double *>(aux) <= RNG::to_double(w[0], w[1])) ? 1 : 0;
@@ -969,6 +964,18 @@ __device__ inline uint32_t select_block(const Params &P, const uint32_t *tb, int
         c = pick ? k.chd[1] : k.chd[0];
     }
     return 0x100u | ((uint32_t)pick << 7) | (uint32_t)c;
+}
+template <int MAXA, bool YV, class RNG, bool LF = false>
+__device__ inline uint32_t select_block(const Params &P, const uint32_t *tb, int b, int depth, int root_visit, float mn, float mx,
+                                        const uint32_t *stage, int used, int staged, const double *pbc_sqrt) {
+    static_assert(MAXA == 2, "one bit for the pick: the block-parallel selection is built for two actions");
+    if constexpr (LF && SMZ_SELECT_LOADS_FIRST) {
+        BlockRaw in;
+        select_block_request<MAXA, YV>(P, tb, b, in);
+        return select_block_decide<MAXA, YV, RNG>(P, b, depth, root_visit, mn, mx, stage, used, staged, pbc_sqrt, in);
+    }
+    Kids<2> k;
+    return select_block_kids<MAXA, YV, RNG>(P, tb, b, depth, root_visit, mn, mx, stage, used, staged, pbc_sqrt, k);
 }
 // The descent over the evaluated blocks, in two steps.  (1) select_chase, by the tree's lane: follow sel[] from the root --
 // ONE dependent LDS read per level -- and leave (block << 8 | pick) of every level in `path`; returns the depth (0: a block on

@@ -50,6 +50,7 @@
 #include "../../include/smz.h"
 #include "smz_device.hpp"
 #include "smz_mlp_device.hpp"
+#include "smz_select_masks.hpp"
 
 using namespace smz;
 
@@ -115,6 +116,10 @@ __device__ inline int pick_lane01(int v, int src) {
     return src ? b : a;
 }
 __device__ inline float pick_lane01(float v, int src) { return __int_as_float(pick_lane01(__float_as_int(v), src)); }
+__device__ inline uint64_t readlane64(uint64_t v, int l) {        // (l: wave-uniform)
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
+    return ((uint64_t)hi << 32) | lo;
+}
 
 // Random-word staging: for each of the wave's 64 trees, all 64 lanes cooperate on that tree's NEXT 64 words --
 // lane j owns word (idx + j) mod 624; words not yet twisted (j >= ready) are twisted in place (every lane reads
@@ -753,6 +758,13 @@ extern __shared__ float4 smz_search_lds4[];
 #ifndef SMZ_EARLY_STAGE
 #define SMZ_EARLY_STAGE 1
 #endif
+// SMZ_SELECT_MASKS: in the LDS-resident two-action instantiations the path through the evaluated blocks is found without a
+// pointer chase -- every block's lane keeps the block's lineage (depth, parent, slot, ancestors as ballot masks) in registers
+// and tests it against two ballots (smz_select_masks.hpp); the path records, the leaf and the parent-row requests come from the
+// lanes that evaluated the blocks.  Searches of up to 64 simulations (two passes); -DSMZ_SELECT_MASKS=0 builds keep the chase.
+#ifndef SMZ_SELECT_MASKS
+#define SMZ_SELECT_MASKS 1
+#endif
 #ifdef SMZ_BPS_PROBE
 #define SMZ_PROBE_DECL unsigned long long pb_t0 = 0, pb_acc[7] = {0, 0, 0, 0, 0, 0, 0};
 #define SMZ_PROBE_START pb_t0 = __builtin_amdgcn_s_memtime();
@@ -939,6 +951,9 @@ __global__ void __launch_bounds__(SMZ_SEARCH_THREADS) k_search_mlp(Params Pin, s
     constexpr int SU = 2;
     const bool split = P.tpw <= SU;
     if (P.sims > 0 && !(dbg & 8)) packed = wave_stage_rng_from<4, PHC>(P, tree, valid, rng_tile, packed, rng.block());
+    // SMZ_SELECT_MASKS: the lineage of the lane's two blocks (lane >> 1 and 32 + (lane >> 1) of tree slot lane & 1)
+    uint32_t lin0 = 0u, lin1 = 0u;                        // smz_masks::lin_pack
+    uint64_t anc0 = 0ull, anc1l = 0ull, anc1h = 0ull;   // ancestors: the first block's (pass 0 only), the second's in pass 0 | 1
     SMZ_PROBE_DECL
     for (int s = 0; s < P.sims; s++) {
         if (INSTR && prof) t0 = __builtin_amdgcn_s_memtime();
@@ -997,7 +1012,148 @@ __global__ void __launch_bounds__(SMZ_SEARCH_THREADS) k_search_mlp(Params Pin, s
         float early_row[kFastTpw] = {0.f, 0.f};
         StagePre<SU> pre;
         bool staged_early = false;            // (wave-uniform) the next round's source words were requested with the parent rows
-        if constexpr (BPS) if (TLDS || ml.sel_on) {
+        // the words the levels of a block-parallel descent of `len` levels drew (all inside the staged window)
+        auto descent_words = [&](int len) {
+            const int nw = select_words(len, A);
+            rng.used += nw; rng.ready -= nw; rng.idx += nw;
+            if (rng.idx >= kMtN) { rng.idx -= kMtN; rng.wrapped(); }
+            packed = rng.pack();
+        };
+        // what both block-parallel descents request once the tree's lane knows its path length (0: the tree takes the sequential
+        // descent) and can name its leaf's parent node (parent_node(), evaluated by the tree's lane)
+        auto early_requests = [&](int len, auto parent_node) {
+#if SMZ_EARLY_ROWS
+            // Round 5: the leaf's PARENT is known here, before the path records, the leaf's action and the stream position are
+            // worked out.  The loads of the wave's two parent rows (global memory: an L2 round trip of ~1.5 k cycles that used
+            // to start only after all of that) are issued now and land in registers while the LDS-only rest of the selection
+            // runs; the network inputs are written from the registers.  The tree phases of this instantiation touch no global
+            // memory, so no later wait of the selection sits behind these loads (gfx950 returns vector-memory loads in order:
+            // profiles/r03_ceiling.md 6b).  A tree that falls back to the sequential descent (bps_all false) takes the old path.
+            bps_all = __ballot(valid && len == 0) == 0ull && __ballot(valid) != 0ull;
+#if SMZ_EARLY_STAGE
+            if (valid && len > 0) descent_words(len);
+#endif
+            if (bps_all) {
+                int par = 0;
+                if (valid && len > 1) par = parent_node();
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");      // (rows stored in earlier rounds may be this round's parents)
+#pragma unroll
+                for (int t = 0; t < kFastTpw; t++) {
+                    const int parent = __builtin_amdgcn_readlane(par, t);
+                    const float *srow = P.hidden + ((size_t)(tree0 + t) * P.N + parent) * P.hs;
+                    early_row[t] = (lane < S && tree0 + t < P.B) ? srow[lane] : 0.f;
+                }
+#if SMZ_EARLY_STAGE
+                if (split && !(dbg & 8)) { stage_issue<SU, PHC>(P, tree, valid, packed, pre); staged_early = true; }
+#endif
+            }
+#endif
+        };
+        // SMZ_SELECT_MASKS (trees in LDS, at most 64 blocks: two passes): no chase.  Each lane keeps the lineage of its two blocks
+        // and finds out from ballots whether they are on this round's path (smz_select_masks.hpp).
+        constexpr bool MASKS = SMZ_SELECT_MASKS && BPS && TLDS;
+        const bool masks_on = MASKS && P.sims <= smz_masks::kMaxBlocks;      // (wave-uniform; longer searches fit with 4-wave workgroups only)
+        if constexpr (MASKS) if (masks_on) {
+            namespace mk = smz_masks;
+            if (s > 0) {
+                // The expansion created block n_exp at depth path_len under the leaf's location (block, slot): the lane that owns
+                // the new block takes its lineage -- the parent's ancestors, held by the parent's lane, and the parent itself.
+                // All indices are wave-uniform per tree slot.
+                int hand = 0;
+                if (valid) {
+                    const int loc = (int)pvals[lane * P.P + h.path_len - 1].x;
+                    hand = h.n_exp | (loc & 0x7f00) | ((loc & 1) << 16) | (h.path_len << 17);
+                }
+#pragma unroll
+                for (int t = 0; t < kFastTpw; t++) {
+                    if (!SMZ_SLOT_VALID(t)) continue;
+                    const int hw = __builtin_amdgcn_readlane(hand, t);
+                    const int e = hw & 255, pb = (hw >> 8) & 255, pl = mk::lane_of(pb, t);
+                    const uint64_t q0 = readlane64(anc0, pl), q1l = readlane64(anc1l, pl), q1h = readlane64(anc1h, pl);
+                    uint64_t a0, a1;
+                    mk::anc_child(pb < 32 ? q0 : q1l, pb < 32 ? 0ull : q1h, pb, t, a0, a1);
+                    const uint32_t lin = mk::lin_pack(hw >> 17, pb, (hw >> 16) & 1);
+                    if (lane == mk::lane_of(e, t)) {
+                        if (e < 32) { lin0 = lin; anc0 = a0; }
+                        else { lin1 = lin; anc1l = a0; anc1h = a1; }
+                    }
+                }
+            }
+            smz_mlp::lds_sync();
+            const int src = lane & 1;
+            const int nexp = pick_lane01(valid ? h.n_exp : -1, src), rvis = pick_lane01(h.root_visit, src);
+            const float bmn = pick_lane01(h.mn, src), bmx = pick_lane01(h.mx, src);
+            const int bused = pick_lane01(valid ? rng.used : 0, src), bstaged = pick_lane01(valid ? rng.staged : 0, src);
+            const int bstage = pick_lane01(valid ? (int)(rng.stage - rng_tile) : 0, src);   // the tree's staged words, as its lane reads them
+            const int nmax = max(__builtin_amdgcn_readlane(valid ? h.n_exp : -1, 0), __builtin_amdgcn_readlane(valid ? h.n_exp : -1, 1));
+            const uint32_t *stb = tree_base(P, tree0 + src);
+            SMZ_PROBE(1)
+            // per pass: select_block's word (0: the block does not exist or was not evaluated) | the leaf action << 9, and the
+            // picked child's (visit, value_sum, reward) -- the words select_record would read back
+            uint32_t r0 = 0u, rv0 = 0u, rs0 = 0u, rw0 = 0u, r1 = 0u, rv1 = 0u, rs1 = 0u, rw1 = 0u;
+            for (int p = 0; p * (kWave / 2) <= nmax; p++) {
+                const int b = p * (kWave / 2) + (lane >> 1);
+                uint32_t r = 0u, rv = 0u, rs = 0u, rw = 0u;
+                if (b <= nexp) {
+                    Kids<2> k;
+                    r = select_block_kids<MAXA, YV, RngT<PHC>>(P, stb, b, mk::lin_depth(p ? lin1 : lin0), rvis, bmn, bmx, rng_tile + bstage, bused,
+                                                               bstaged, pbc_lds, k);
+                    if (r) {
+                        const bool pk = (r & 0x80u) != 0u;
+                        rv = (uint32_t)(pk ? k.vis[1] : k.vis[0]);
+                        rs = __float_as_uint(pk ? k.vsum[1] : k.vsum[0]);
+                        rw = __float_as_uint(pk ? k.rew[1] : k.rew[0]);
+                        r |= (uint32_t)(b == 0 ? (int)pk : (pk ? k.act[1] : k.act[0])) << 9;       // (the root's child j is action j)
+                    }
+                }
+                if (p == 0) { r0 = r; rv0 = rv; rs0 = rs; rw0 = rw; }
+                else { r1 = r; rv1 = rv; rs1 = rs; rw1 = rw; }
+            }
+            SMZ_PROBE(2)
+            const int b0 = lane >> 1, b1 = kWave / 2 + (lane >> 1);
+            const uint64_t p0 = __ballot((r0 & 0x80u) != 0u), p1 = __ballot((r1 & 0x80u) != 0u);
+            const bool gd0 = b0 <= nexp && mk::good(b0, lin0, src, p0, p1), gd1 = b1 <= nexp && mk::good(b1, lin1, src, p0, p1);
+            const uint64_t g0 = __ballot(gd0), g1 = __ballot(gd1);
+            const bool on0 = mk::on_path(gd0, anc0, 0ull, g0, g1), on1 = mk::on_path(gd1, anc1l, anc1h, g0, g1);
+            const bool ok0 = (r0 & 0x100u) != 0u, ok1 = (r1 & 0x100u) != 0u;
+            // a block on the path whose level's words lie beyond the staged window: its tree takes the sequential descent
+            const uint64_t fb = __ballot((on0 && !ok0) || (on1 && !ok1));
+            // the path's last block: its picked child has no block yet.  Its lane knows the leaf, the path length and the
+            // leaf's parent node -- one word, handed to the tree's lane
+            const bool lf0 = on0 && ok0 && (r0 & 127u) == 0u, lf1 = on1 && ok1 && (r1 & 127u) == 0u;
+            const uint64_t lf = __ballot(lf0 || lf1);
+            const uint32_t mine = lf0 ? mk::leaf_pack(b0, lin0, (r0 >> 7) & 1u, (r0 >> 9) & 1u, A) : mk::leaf_pack(b1, lin1, (r1 >> 7) & 1u, (r1 >> 9) & 1u, A);
+            uint32_t lw = 0u;
+#pragma unroll
+            for (int t = 0; t < kFastTpw; t++) {
+                const int ll = mk::leaf_lane(lf, t);
+                if ((fb & mk::tree_lanes(t)) == 0ull && ll >= 0) {
+                    const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)mine, ll);
+                    if (lane == t) lw = w;
+                }
+            }
+            const int len = valid ? mk::leaf_len(lw) : 0;
+            SMZ_PROBE(3)
+            early_requests(len, [&] { return mk::leaf_parent(lw); });
+            // the path records, from the registers of the lanes on the path (record d: the block at depth d)
+            if ((fb & mk::tree_lanes(src)) == 0ull) {
+                if (on0) pvals[src * P.P + mk::lin_depth(lin0)] = make_uint4((uint32_t)(b0 << 8) | ((r0 >> 7) & 1u), rv0, rs0, rw0);
+                if (on1) pvals[src * P.P + mk::lin_depth(lin1)] = make_uint4((uint32_t)(b1 << 8) | ((r1 >> 7) & 1u), rv1, rs1, rw1);
+            }
+            if (valid && len > 0) {
+                const int loc = mk::leaf_loc(lw);
+                L.leaf_id = mk::child_node(loc >> 8, loc & 1, A);
+                L.parent_id = len > 1 ? mk::leaf_parent(lw) : 0;
+                L.action = mk::leaf_action(lw);
+                L.branch = depth_flag(len - 1);
+#if !(SMZ_EARLY_ROWS && SMZ_EARLY_STAGE)
+                descent_words(len);
+#endif
+                h.path_len = len;
+                bps_done = true;
+            }
+        }
+        if constexpr (BPS) if (!masks_on && (TLDS || ml.sel_on)) {
             uint16_t *selw = reinterpret_cast<uint16_t *>(scratch + ml.sel_off);          // [tpw][sel_n]
             const int SELN = ml.sel_n;
             if (valid && s > 0) selw[lane * SELN + h.n_exp] = (uint16_t)(h.path_len << 9);   // depth of the node the expansion created
@@ -1057,38 +1213,7 @@ __global__ void __launch_bounds__(SMZ_SEARCH_THREADS) k_search_mlp(Params Pin, s
             smz_mlp::lds_sync();
             SMZ_PROBE(3)
             const int blen = pick_lane01(len, src);
-#if SMZ_EARLY_ROWS
-            // Round 5: the leaf's PARENT is the path's last-but-one entry -- known here, before the path records, the leaf's
-            // action and the stream position are worked out.  The loads of the wave's two parent rows (global memory: an L2 round
-            // trip of ~1.5 k cycles that used to start only after all of that) are issued now and land in registers while the
-            // LDS-only rest of the selection runs; the network inputs are written from the registers.  The tree phases of this
-            // instantiation touch no global memory, so no later wait of the selection sits behind these loads (gfx950 returns
-            // vector-memory loads in order: profiles/r03_ceiling.md 6b).  A tree that falls back to the sequential descent
-            // (bps_all false) takes the old path.
-            bps_all = __ballot(valid && len == 0) == 0ull && __ballot(valid) != 0ull;
-#if SMZ_EARLY_STAGE
-            if (valid && len > 0) {                                     // the words the descent's levels drew (all inside the staged window)
-                const int nw = select_words(len, A);
-                rng.used += nw; rng.ready -= nw; rng.idx += nw;
-                if (rng.idx >= kMtN) { rng.idx -= kMtN; rng.wrapped(); }
-                packed = rng.pack();
-            }
-#endif
-            if (bps_all) {
-                int par = 0;
-                if (valid && len > 1) { const int loc = pathw[lane * SELN + len - 2], pb = loc >> 8; par = pb == 0 ? 1 + (loc & 3) : 1 + A + (pb - 1) * 2 + (loc & 3); }
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");      // (rows stored in earlier rounds may be this round's parents)
-#pragma unroll
-                for (int t = 0; t < kFastTpw; t++) {
-                    const int parent = __builtin_amdgcn_readlane(par, t);
-                    const float *srow = P.hidden + ((size_t)(tree0 + t) * P.N + parent) * P.hs;
-                    early_row[t] = (lane < S && tree0 + t < P.B) ? srow[lane] : 0.f;
-                }
-#if SMZ_EARLY_STAGE
-                if (split && !(dbg & 8)) { stage_issue<SU, PHC>(P, tree, valid, packed, pre); staged_early = true; }
-#endif
-            }
-#endif
+            early_requests(len, [&] { const int loc = pathw[lane * SELN + len - 2], pb = loc >> 8; return pb == 0 ? 1 + (loc & 3) : 1 + A + (pb - 1) * 2 + (loc & 3); });
             // (trees in global memory: the leaf's action word is requested BEFORE the path records' words, so the two L2 round trips
             //  overlap -- the records' loop waits for its own loads, and the leaf's used to start only behind that wait)
             if constexpr (!TLDS && SMZ_LEAF_FIRST) { if (valid && len > 0) L = select_leaf(P, stb, pathw + lane * SELN, len); }
@@ -1096,10 +1221,7 @@ __global__ void __launch_bounds__(SMZ_SEARCH_THREADS) k_search_mlp(Params Pin, s
             if (valid && len > 0) {
                 if constexpr (TLDS || !SMZ_LEAF_FIRST) L = select_leaf(P, stb, pathw + lane * SELN, len);
 #if !(SMZ_EARLY_ROWS && SMZ_EARLY_STAGE)
-                const int nw = select_words(len, A);                    // the words the descent's levels drew (all inside the staged window)
-                rng.used += nw; rng.ready -= nw; rng.idx += nw;
-                if (rng.idx >= kMtN) { rng.idx -= kMtN; rng.wrapped(); }
-                packed = rng.pack();
+                descent_words(len);
 #endif
                 h.path_len = len;
                 bps_done = true;

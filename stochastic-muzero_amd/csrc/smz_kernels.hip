@@ -1790,6 +1790,52 @@ int launch_check() {
     return SMZ_OK;
 }
 
+// ---- the host path the single-launch searches share (every SMZ_PART, and the files that include this one as SMZ_PART 5) ----
+// Refusals that are word for word the same in every search; `who` is the entry point or launcher the message names.
+int refuse_large_actions(const char *who) { return fail(SMZ_ERR_TOO_LARGE, "%s: large-action handles search step-wise only", who); }
+int refuse_multi_player(const char *who) { return fail(SMZ_ERR_INVALID, "%s: multi-player handles search step-wise only", who); }
+int check_dirichlet_alpha(const smz_handle *h, int train) {
+    if (train && h->cfg.num_simulations > 0 && !(h->cfg.root_dirichlet_alpha > 0))
+        return fail(SMZ_ERR_INVALID, "root_dirichlet_alpha must be > 0 to draw noise (numpy raises ValueError)%s");
+    return SMZ_OK;
+}
+
+// The power table of `temperature` for act_tree (smz_act, and the searches that act in their tail): a new temperature is a
+// synchronous upload (not capturable); the table is reused while the temperature is unchanged.
+int use_pow_table(smz_handle *h, Params &P, double temperature, const double *pow_table_host, smz_stream stream) {
+    if (!pow_table_host || !(temperature >= 0.3)) return SMZ_OK;
+    if (!h->pow_valid || h->pow_T != temperature) {
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        HIP_TRY(hipMemcpy(h->d_pow, pow_table_host, ((size_t)h->cfg.num_simulations + 1) * sizeof(double), hipMemcpyHostToDevice));
+        h->pow_T = temperature;
+        h->pow_valid = true;
+    }
+    P.pow_table = h->d_pow;
+    return SMZ_OK;
+}
+
+// Launches the instantiation `Kern` with `lds` bytes of dynamic LDS.  The opt-in above the default limit is a host-side call:
+// made once per instantiation and device, and again only when a launch needs more.
+template <auto Kern, class... Args>
+int launch_with_lds(smz_handle *h, int blocks, int threads, size_t lds, smz_stream stream, Args... args) {
+    static size_t granted_dev[64] = {};
+    size_t &granted = granted_dev[h->cfg.device & 63];
+    if (lds > granted) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return fail(SMZ_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS) failed%s");
+        granted = lds;
+    }
+    hipLaunchKernelGGL(Kern, dim3(blocks), dim3(threads), lds, (hipStream_t)stream, args...);
+    return SMZ_OK;
+}
+
+// what every search launcher ends with: the tree is there for smz_root_stats / smz_act, no selection is pending
+int search_launched(smz_handle *h) {
+    h->root_ready = true;
+    h->selected = false;
+    return launch_check();
+}
+
 // dispatch on the per-lane scratch bucket (smallest MAXA >= A)
 #define SMZ_DISPATCH(maxa, ...)               \
     switch (maxa) {                           \
@@ -2224,6 +2270,12 @@ struct SearchActArgs {       // ActOut (+ the fused env step) across the transla
     EnvStep env;             // env.state == nullptr: no env step in the launch
 };
 }  // extern "C" (internal C++ linkage for the two launchers)
+// smz_last_kernel's text for an instantiation of the handle's action bucket, as rocprofv3 prints it (U = 1 everywhere)
+static void name_search_mlp(smz_handle *h, int ks, bool instr, bool aex, bool msk, bool phx, bool tlds) {
+    const auto b = [](bool v) { return v ? "true" : "false"; };
+    snprintf(h->last_kernel, sizeof(h->last_kernel), "k_search_mlp<%d, %d, 1, %s, %s, %s, %s, %s>", h->maxa, ks, b(instr), b(aex),
+             b(msk), b(phx), b(tlds));
+}
 int smz_internal_search_launch_narrow(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev,
                                       int train, SearchActArgs a, const double *pow_table_host, smz_stream stream);
 int smz_internal_search_launch_wide(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev,
@@ -2237,28 +2289,14 @@ int smz_internal_search_launch_tlds(smz_handle *h, const smz_mlp_desc *desc, con
 int smz_internal_search_launch_tlds(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev,
                                     int train, SearchActArgs a, Params P, int kWaves, int blocks, size_t lds_t, smz_stream stream) {
     const ActOut act = {a.temperature, a.action, a.policy, a.child_visits, a.root_value};
-#define SMZ_LAUNCH_TLDS(MA, MSK, PHX)                                                                                  \
-    {                                                                                                                  \
-        static size_t granted_dev[64] = {};                                                                            \
-        size_t &granted = granted_dev[h->cfg.device & 63];                                                             \
-        if (lds_t > granted) {                                                                                         \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_mlp<MA, 2, 1, false, true, MSK, PHX, true>), \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t) != hipSuccess)             \
-                return fail(SMZ_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS) failed%s");                            \
-            granted = lds_t;                                                                                           \
-        }                                                                                                              \
-        hipLaunchKernelGGL((k_search_mlp<MA, 2, 1, false, true, MSK, PHX, true>), dim3(blocks), dim3(kWaves * kWave),  \
-                           lds_t, (hipStream_t)stream, P, *desc, weights_dev, obs_dev, train, act, a.env);             \
-        snprintf(h->last_kernel, sizeof(h->last_kernel), "k_search_mlp<%d, 2, 1, false, true, %s, %s, true>", MA,      \
-                 MSK ? "true" : "false", PHX ? "true" : "false");                                                      \
-    }
-    if (h->maxa == 2) {
-        if (P.philox) SMZ_LAUNCH_TLDS(2, true, true) else SMZ_LAUNCH_TLDS(2, true, false)
-    } else {
-        if (P.philox) SMZ_LAUNCH_TLDS(4, true, true) else SMZ_LAUNCH_TLDS(4, true, false)
-    }
+#define SMZ_LAUNCH_TLDS(MA, PHX)                                                                                       \
+    launch_with_lds<k_search_mlp<MA, 2, 1, false, true, true, PHX, true>>(h, blocks, kWaves * kWave, lds_t, stream, P, *desc, \
+                                                                          weights_dev, obs_dev, train, act, a.env)
+    const int rc = h->maxa == 2 ? (P.philox ? SMZ_LAUNCH_TLDS(2, true) : SMZ_LAUNCH_TLDS(2, false))
+                                : (P.philox ? SMZ_LAUNCH_TLDS(4, true) : SMZ_LAUNCH_TLDS(4, false));
 #undef SMZ_LAUNCH_TLDS
-    return SMZ_OK;
+    if (rc == SMZ_OK) name_search_mlp(h, 2, false, true, true, P.philox != 0, true);
+    return rc;
 }
 #endif
 #if SMZ_PART != 6
@@ -2274,22 +2312,11 @@ int SMZ_SEARCH_LAUNCH(smz_handle *h, const smz_mlp_desc *desc, const float *weig
         return fail(SMZ_ERR_INVALID, "smz_search_mlp: descriptor does not describe an LDS-resident network%s");
     if (desc->A != h->P.A || desc->S != h->P.S)
         return fail(SMZ_ERR_INVALID, "smz_search_mlp: network dimensions differ from the handle's%s");
-    if (train && h->cfg.num_simulations > 0 && !(h->cfg.root_dirichlet_alpha > 0))
-        return fail(SMZ_ERR_INVALID, "root_dirichlet_alpha must be > 0 to draw noise (numpy raises ValueError)%s");
+    if (const int rc = check_dirichlet_alpha(h, train)) return rc;
     DeviceGuard guard(h->cfg.device);
     int kWaves = 8;
     if (const char *e = getenv("SMZ_SEARCH_WAVES")) { const int v = atoi(e); if ((v == 1 || v == 2 || v == 4 || v == 8 || v == 12 || v == 16) && v * kWave <= SMZ_SEARCH_THREADS) kWaves = v; }
     Params P = h->P;
-    if (act.action && pow_table_host && act.temperature >= 0.3) {       // as smz_act: the power table of this temperature
-        if (!h->pow_valid || h->pow_T != act.temperature) {
-            HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-            HIP_TRY(hipMemcpy(h->d_pow, pow_table_host, ((size_t)h->cfg.num_simulations + 1) * sizeof(double),
-                              hipMemcpyHostToDevice));
-            h->pow_T = act.temperature;
-            h->pow_valid = true;
-        }
-        P.pow_table = h->d_pow;
-    }
     // trees per wave: the smallest power of two that covers B with 256 workgroups of 8 waves, capped at 2 -- beyond
     // 4096 trees the grid simply has more workgroups than CUs and they run one after another (each re-stages the
     // weights, ~1 % of its run time): per-wave LDS buffers stay small and the specialised instantiation applies.
@@ -2300,22 +2327,15 @@ int SMZ_SEARCH_LAUNCH(smz_handle *h, const smz_mlp_desc *desc, const float *weig
     const MegaLds ml = mega_lds(*desc, P, tpw, false, kWaves);
     const size_t lds = ((size_t)ml.wave_off + (size_t)kWaves * ml.per_wave) * sizeof(float);
     if (lds > 160 * 1024) return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp: working set exceeds the 160 KB LDS of a CU%s");
-    const int blocks = (P.B + kWaves * tpw - 1) / (kWaves * tpw);
-#define SMZ_LAUNCH_SEARCH(UU, INSTR, AEX, MSK, PHX)                                                                    \
-    SMZ_SEARCH_DISPATCH2(h->maxa, h->K, {                                                                              \
-        static size_t granted_dev[64] = {}; /* per instantiation and device: the opt-in is a host-side call */           \
-        size_t &granted = granted_dev[h->cfg.device & 63];                                                             \
-        if (lds > granted) {                                                                                           \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_mlp<MA, KS, UU, INSTR, AEX, MSK, PHX>),    \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)               \
-                return fail(SMZ_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS) failed%s");                            \
-            granted = lds;                                                                                             \
-        }                                                                                                              \
-        hipLaunchKernelGGL((k_search_mlp<MA, KS, UU, INSTR, AEX, MSK, PHX>), dim3(blocks), dim3(kWaves * kWave), lds,  \
-                           (hipStream_t)stream, P, *desc, weights_dev, obs_dev, train, act, a.env);                    \
-        snprintf(h->last_kernel, sizeof(h->last_kernel), "k_search_mlp<%d, %d, %d, %s, %s, %s, %s, false>", MA, KS, UU, \
-                 INSTR ? "true" : "false", AEX ? "true" : "false", MSK ? "true" : "false", PHX ? "true" : "false");     \
-    })
+    if (act.action && use_pow_table(h, P, act.temperature, pow_table_host, stream) != SMZ_OK) return SMZ_ERR_HIP;
+    const int blocks = (P.B + kWaves * tpw - 1) / (kWaves * tpw), threads = kWaves * kWave;
+    int rc = SMZ_OK;
+#define SMZ_LAUNCH_SEARCH(INSTR, AEX, MSK, PHX)                                                                        \
+    {                                                                                                                  \
+        SMZ_SEARCH_DISPATCH2(h->maxa, h->K, rc = (launch_with_lds<k_search_mlp<MA, KS, 1, INSTR, AEX, MSK, PHX>>(      \
+                                                h, blocks, threads, lds, stream, P, *desc, weights_dev, obs_dev, train, act, a.env))); \
+        if (rc == SMZ_OK) name_search_mlp(h, h->K == 2 ? 2 : 0, INSTR, AEX, MSK, PHX, false);                          \
+    }
     // smz_mlp_layout only accepts OP == 64 (one output neuron per lane): U = 1.  The instrumented instantiation runs
     // when level statistics are enabled (smz_enable_stats) or a SMZ_DEBUG_SKIP switch is set.
     // (the specialised instantiation is the parity-mode path: a Philox handle runs the generic one)
@@ -2334,43 +2354,28 @@ int SMZ_SEARCH_LAUNCH(smz_handle *h, const smz_mlp_desc *desc, const float *weig
         if (tlds) P.stats = h->d_stats;              // (the production kernel carries no level statistics: only the probe's stamps land there)
 #endif
         if (tlds && (P.active || P.philox)) {        // masked / Philox handles: SMZ_PART 6
-            const int rc = smz_internal_search_launch_tlds(h, desc, weights_dev, obs_dev, train, a, P, kWaves, blocks, lds_t, stream);
-            if (rc != SMZ_OK) return rc;
-            h->root_ready = true;
-            h->selected = false;
-            return launch_check();
+            rc = smz_internal_search_launch_tlds(h, desc, weights_dev, obs_dev, train, a, P, kWaves, blocks, lds_t, stream);
+            return rc != SMZ_OK ? rc : search_launched(h);
         }
 #if SMZ_PART == 0 || SMZ_PART == 2
         if (tlds) {                                  // the plain instantiation (the headline's) stays in this translation unit
 #define SMZ_LAUNCH_TLDS(MA)                                                                                            \
-            {                                                                                                          \
-                static size_t granted_dev[64] = {};                                                                    \
-                size_t &granted = granted_dev[h->cfg.device & 63];                                                     \
-                if (lds_t > granted) {                                                                                 \
-                    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_mlp<MA, 2, 1, false, true, false, false, true>), \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t) != hipSuccess)     \
-                        return fail(SMZ_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS) failed%s");                    \
-                    granted = lds_t;                                                                                   \
-                }                                                                                                      \
-                hipLaunchKernelGGL((k_search_mlp<MA, 2, 1, false, true, false, false, true>), dim3(blocks),            \
-                                   dim3(kWaves * kWave), lds_t, (hipStream_t)stream, P, *desc, weights_dev, obs_dev, train, \
-                                   act, a.env);                                                                        \
-                snprintf(h->last_kernel, sizeof(h->last_kernel), "k_search_mlp<%d, 2, 1, false, true, false, false, true>", MA); \
-            }
-            if (h->maxa == 2) SMZ_LAUNCH_TLDS(2) else SMZ_LAUNCH_TLDS(4)
+            launch_with_lds<k_search_mlp<MA, 2, 1, false, true, false, false, true>>(h, blocks, threads, lds_t, stream, P, *desc, \
+                                                                                     weights_dev, obs_dev, train, act, a.env)
+            rc = h->maxa == 2 ? SMZ_LAUNCH_TLDS(2) : SMZ_LAUNCH_TLDS(4);
 #undef SMZ_LAUNCH_TLDS
-            h->root_ready = true;
-            h->selected = false;
-            return launch_check();
+            if (rc != SMZ_OK) return rc;
+            name_search_mlp(h, 2, false, true, false, false, true);
+            return search_launched(h);
         }
 #endif
     }
     if ((P.stats || P.dbg) && fast && !P.philox && (P.dbg & 32) && h->maxa == 2 && h->K == 2) {
         // phase stamps of the specialised instantiation itself (SMZ_DEBUG_SKIP=48), for the headline geometry only
         constexpr int MA = 2, KS = 2;
-        hipLaunchKernelGGL((k_search_mlp<MA, KS, 1, true, true>), dim3(blocks), dim3(kWaves * kWave), lds, (hipStream_t)stream,
+        hipLaunchKernelGGL((k_search_mlp<MA, KS, 1, true, true>), dim3(blocks), dim3(threads), lds, (hipStream_t)stream,
                            P, *desc, weights_dev, obs_dev, train, act, a.env);
-        snprintf(h->last_kernel, sizeof(h->last_kernel), "k_search_mlp<2, 2, 1, true, true, true, false, false>");
+        name_search_mlp(h, 2, true, true, true, false, false);
     } else
 #endif
 #if (SMZ_PART == 0 || SMZ_PART == 2) && SMZ_KS4
@@ -2380,35 +2385,20 @@ int SMZ_SEARCH_LAUNCH(smz_handle *h, const smz_mlp_desc *desc, const float *weig
     // Plain, masked (smz_set_active) and Philox handles.
     if (fast && !(P.stats || P.dbg) && h->maxa == 4 && h->K == 4) {
 #define SMZ_LAUNCH_KS4(MSK, PHX)                                                                                       \
-        {                                                                                                              \
-            static size_t granted_dev[64] = {};                                                                        \
-            size_t &granted = granted_dev[h->cfg.device & 63];                                                         \
-            if (lds > granted) {                                                                                       \
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_mlp<4, 4, 1, false, true, MSK, PHX>),  \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)           \
-                    return fail(SMZ_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS) failed%s");                        \
-                granted = lds;                                                                                         \
-            }                                                                                                          \
-            hipLaunchKernelGGL((k_search_mlp<4, 4, 1, false, true, MSK, PHX>), dim3(blocks), dim3(kWaves * kWave), lds, \
-                               (hipStream_t)stream, P, *desc, weights_dev, obs_dev, train, act, a.env);                \
-            snprintf(h->last_kernel, sizeof(h->last_kernel), "k_search_mlp<4, 4, 1, false, true, %s, %s, false>",      \
-                     MSK ? "true" : "false", PHX ? "true" : "false");                                                  \
-        }
-        if (P.philox) SMZ_LAUNCH_KS4(true, true)
-        else if (P.active) SMZ_LAUNCH_KS4(true, false)
-        else SMZ_LAUNCH_KS4(false, false)
+        launch_with_lds<k_search_mlp<4, 4, 1, false, true, MSK, PHX>>(h, blocks, threads, lds, stream, P, *desc, weights_dev, \
+                                                                      obs_dev, train, act, a.env)
+        rc = P.philox ? SMZ_LAUNCH_KS4(true, true) : P.active ? SMZ_LAUNCH_KS4(true, false) : SMZ_LAUNCH_KS4(false, false);
 #undef SMZ_LAUNCH_KS4
+        if (rc == SMZ_OK) name_search_mlp(h, 4, false, true, P.philox || P.active, P.philox != 0, false);
     } else
 #endif
-    if (P.stats || P.dbg) { SMZ_LAUNCH_SEARCH(1, true, false, true, false); }
-    else if (fast && P.philox) { SMZ_LAUNCH_SEARCH(1, false, true, true, true); }
-    else if (fast && !P.active) { SMZ_LAUNCH_SEARCH(1, false, true, false, false); }
-    else if (fast) { SMZ_LAUNCH_SEARCH(1, false, true, true, false); }
-    else { SMZ_LAUNCH_SEARCH(1, false, false, true, false); }
+    if (P.stats || P.dbg) SMZ_LAUNCH_SEARCH(true, false, true, false)
+    else if (fast && P.philox) SMZ_LAUNCH_SEARCH(false, true, true, true)
+    else if (fast && !P.active) SMZ_LAUNCH_SEARCH(false, true, false, false)
+    else if (fast) SMZ_LAUNCH_SEARCH(false, true, true, false)
+    else SMZ_LAUNCH_SEARCH(false, false, true, false)
 #undef SMZ_LAUNCH_SEARCH
-    h->root_ready = true;
-    h->selected = false;
-    return launch_check();
+    return rc != SMZ_OK ? rc : search_launched(h);
 }
 #endif  // SMZ_PART != 6
 
@@ -2416,8 +2406,8 @@ extern "C" {
 #if SMZ_PART != 4 && SMZ_PART != 6
 int smz_search_mlp(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, int train,
                    smz_stream stream) {
-    if (h && h->large_actions) return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp: large-action handles search step-wise only%s");
-    if (h && h->P.n_cycle > 1) return fail(SMZ_ERR_INVALID, "smz_search_mlp: multi-player handles search step-wise only%s");
+    if (h && h->large_actions) return refuse_large_actions("smz_search_mlp");
+    if (h && h->P.n_cycle > 1) return refuse_multi_player("smz_search_mlp");
     return smz_internal_search_launch_narrow(h, desc, weights_dev, obs_dev, train,
                                              SearchActArgs{0.0, nullptr, nullptr, nullptr, nullptr, EnvStep{}}, nullptr, stream);
 }
@@ -2425,9 +2415,9 @@ int smz_search_mlp(smz_handle *h, const smz_mlp_desc *desc, const float *weights
 int smz_search_mlp_act(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, int train,
                        double temperature, const double *pow_table_host, int32_t *action_dev, double *policy_dev,
                        double *child_visits_dev, float *root_value_dev, smz_stream stream) {
-    if (h && h->large_actions) return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp_act: large-action handles search step-wise only%s");
+    if (h && h->large_actions) return refuse_large_actions("smz_search_mlp_act");
     if (!action_dev || !policy_dev || !child_visits_dev) return fail(SMZ_ERR_INVALID, "smz_search_mlp_act: null output%s");
-    if (h && h->P.n_cycle > 1) return fail(SMZ_ERR_INVALID, "smz_search_mlp_act: multi-player handles search step-wise only%s");
+    if (h && h->P.n_cycle > 1) return refuse_multi_player("smz_search_mlp_act");
     return smz_internal_search_launch_narrow(h, desc, weights_dev, obs_dev, train,
                                              SearchActArgs{temperature, action_dev, policy_dev, child_visits_dev, root_value_dev,
                                                            EnvStep{}},
@@ -2438,14 +2428,12 @@ int smz_search_mlp_act_cartpole(smz_handle *h, const smz_mlp_desc *desc, const f
                                 double temperature, const double *pow_table_host, int32_t *action_dev, double *policy_dev,
                                 double *child_visits_dev, float *root_value_dev, const smz_cartpole_env *env,
                                 smz_stream stream) {
-    if (h && h->large_actions)
-        return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp_act_cartpole: large-action handles search step-wise only%s");
+    if (h && h->large_actions) return refuse_large_actions("smz_search_mlp_act_cartpole");
     if (!action_dev || !policy_dev || !child_visits_dev || !root_value_dev || !env || !env->state_dev || !env->obs_dev)
         return fail(SMZ_ERR_INVALID, "smz_search_mlp_act_cartpole: null argument%s");
     if (!h || !desc || h->P.A != 2 || desc->obs != 4)
         return fail(SMZ_ERR_INVALID, "smz_search_mlp_act_cartpole: the built-in env has 4 observations and 2 actions%s");
-    if (h->P.n_cycle > 1)
-        return fail(SMZ_ERR_INVALID, "smz_search_mlp_act_cartpole: multi-player handles search step-wise only%s");
+    if (h->P.n_cycle > 1) return refuse_multi_player("smz_search_mlp_act_cartpole");
     const smz_episode_ctl *c = env->ctl;
     if (c && (!c->step_count_dev || c->on_end < 0 || c->on_end > 2 || (c->on_end == 2 && !c->episode_dev) ||
               (c->on_end == 1 && !c->active_dev)))
@@ -2483,17 +2471,7 @@ int smz_act(smz_handle *h, double temperature, const double *pow_table_host, int
     if (!h->root_ready) return fail(SMZ_ERR_STATE, "smz_act before smz_root_init%s");
     DeviceGuard guard(h->cfg.device);
     Params P = h->P;
-    if (pow_table_host && temperature >= 0.3) {
-        if (!h->pow_valid || h->pow_T != temperature) {
-            // a new temperature: synchronous upload (not capturable); the table is reused while T is unchanged
-            HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-            HIP_TRY(hipMemcpy(h->d_pow, pow_table_host, ((size_t)h->cfg.num_simulations + 1) * sizeof(double),
-                              hipMemcpyHostToDevice));
-            h->pow_T = temperature;
-            h->pow_valid = true;
-        }
-        P.pow_table = h->d_pow;
-    }
+    if (use_pow_table(h, P, temperature, pow_table_host, stream) != SMZ_OK) return SMZ_ERR_HIP;
     if (h->large_actions) return smz_internal_la_act(h, P, temperature, action_dev, policy_dev, child_visits_dev, root_value_dev, stream);
     SMZ_DISPATCH(h->maxa, hipLaunchKernelGGL((k_act<MA>), tree_grid(P.B), dim3(kWave), 0, (hipStream_t)stream, P, temperature,
                                              action_dev, policy_dev, child_visits_dev, root_value_dev));

@@ -220,28 +220,18 @@ __global__ void __launch_bounds__(kWavesPerWg *kWave, kWgPerCu) k_search_lstm(Pa
 
 int search_lstm_launch(smz_handle *h, const smz_lstm_desc *desc, const float *weights_dev, const float *hidden0_dev,
                        const float *policy0_dev, int train, ActOut act, const double *pow_table_host, smz_stream stream) {
-    if (h && h->large_actions) return fail(SMZ_ERR_TOO_LARGE, "smz_search_lstm: large-action handles search step-wise only%s");
+    if (h && h->large_actions) return refuse_large_actions("smz_search_lstm");
     if (!h || !desc || !weights_dev || !hidden0_dev || !policy0_dev) return fail(SMZ_ERR_INVALID, "smz_search_lstm: null argument%s");
-    if (h->P.n_cycle > 1) return fail(SMZ_ERR_INVALID, "smz_search_lstm: multi-player handles search step-wise only%s");
+    if (h->P.n_cycle > 1) return refuse_multi_player("smz_search_lstm");
     if (smz_lstm::desc_check(desc, weights_dev) != SMZ_OK)
         return fail(SMZ_ERR_INVALID, "smz_search_lstm: descriptor does not describe an lstm_model weight buffer%s");
     if (desc->A != h->P.A || desc->S != h->P.S)
         return fail(SMZ_ERR_INVALID, "smz_search_lstm: network dimensions differ from the handle's%s");
     if (h->maxa > 4 || h->P.A != h->maxa)
         return fail(SMZ_ERR_TOO_LARGE, "smz_search_lstm: outside the single-launch kernel's limits (2 or 4 actions): use the step-wise entry points%s");
-    if (train && h->cfg.num_simulations > 0 && !(h->cfg.root_dirichlet_alpha > 0))
-        return fail(SMZ_ERR_INVALID, "root_dirichlet_alpha must be > 0 to draw noise (numpy raises ValueError)%s");
+    if (const int rc = check_dirichlet_alpha(h, train)) return rc;
     DeviceGuard guard(h->cfg.device);
     Params P = h->P;
-    if (act.action && pow_table_host && act.temperature >= 0.3) {
-        if (!h->pow_valid || h->pow_T != act.temperature) {
-            HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-            HIP_TRY(hipMemcpy(h->d_pow, pow_table_host, ((size_t)h->cfg.num_simulations + 1) * sizeof(double), hipMemcpyHostToDevice));
-            h->pow_T = act.temperature;
-            h->pow_valid = true;
-        }
-        P.pow_table = h->d_pow;
-    }
     // two workgroups per CU before a wave takes a second tree
     const int waves = kWgPerCu * kCus * kWavesPerWg;
     const int tpw = (P.B + waves - 1) / waves;
@@ -250,32 +240,20 @@ int search_lstm_launch(smz_handle *h, const smz_lstm_desc *desc, const float *we
     const LstmLds ml = lstm_lds(*desc, P, tpw);
     const size_t lds = (size_t)ml.total * sizeof(float);
     if (lds > 160 * 1024) return fail(SMZ_ERR_TOO_LARGE, "smz_search_lstm: working set exceeds the 160 KB LDS of a CU%s");
-    const int blocks = (P.B + kWavesPerWg * tpw - 1) / (kWavesPerWg * tpw);
-#define SMZ_LAUNCH_LS(MA) { if (h->K == 2) SMZ_LAUNCH_LS1(MA, 2) else SMZ_LAUNCH_LS1(MA, 0) }
-#define SMZ_LAUNCH_LS1(MA, KK) { if (P.philox) SMZ_LAUNCH_LS2(MA, true, KK) else SMZ_LAUNCH_LS2(MA, false, KK) }
-#define SMZ_LAUNCH_LS2(MA, PX, KK)                                                                                     \
-    {                                                                                                                  \
-        static size_t granted_dev[64] = {};                                                                            \
-        size_t &granted = granted_dev[h->cfg.device & 63];                                                             \
-        if (lds > granted) {                                                                                           \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_lstm<MA, PX, KK>),                         \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)               \
-                return fail(SMZ_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS) failed%s");                             \
-            granted = lds;                                                                                             \
-        }                                                                                                              \
-        hipLaunchKernelGGL((k_search_lstm<MA, PX, KK>), dim3(blocks), dim3(kWavesPerWg * kWave), lds, (hipStream_t)stream, P, \
-                           *desc, weights_dev, hidden0_dev, policy0_dev, train, act);                                  \
-        if (KK) snprintf(h->last_kernel, sizeof(h->last_kernel), "k_search_lstm<%d, %s, %d>", MA, PX ? "true" : "false", KK); \
-        else snprintf(h->last_kernel, sizeof(h->last_kernel), PX ? "k_search_lstm<%d, true>" : "k_search_lstm<%d>", MA); \
-    }
-    if (h->maxa == 2) SMZ_LAUNCH_LS(2)
-    else SMZ_LAUNCH_LS(4)
+    if (act.action && use_pow_table(h, P, act.temperature, pow_table_host, stream) != SMZ_OK) return SMZ_ERR_HIP;
+    const int blocks = (P.B + kWavesPerWg * tpw - 1) / (kWavesPerWg * tpw), ks = h->K == 2 ? 2 : 0;
+#define SMZ_LAUNCH_LS(MA, KK) (P.philox ? SMZ_LAUNCH_LS1(MA, true, KK) : SMZ_LAUNCH_LS1(MA, false, KK))
+#define SMZ_LAUNCH_LS1(MA, PX, KK)                                                                                     \
+    launch_with_lds<k_search_lstm<MA, PX, KK>>(h, blocks, kWavesPerWg * kWave, lds, stream, P, *desc, weights_dev, hidden0_dev, \
+                                               policy0_dev, train, act)
+    const int rc = h->maxa == 2 ? (ks ? SMZ_LAUNCH_LS(2, 2) : SMZ_LAUNCH_LS(2, 0)) : (ks ? SMZ_LAUNCH_LS(4, 2) : SMZ_LAUNCH_LS(4, 0));
 #undef SMZ_LAUNCH_LS
 #undef SMZ_LAUNCH_LS1
-#undef SMZ_LAUNCH_LS2
-    h->root_ready = true;
-    h->selected = false;
-    return launch_check();
+    if (rc != SMZ_OK) return rc;
+    // (the name as rocprofv3 prints it: without the defaulted arguments)
+    if (ks) snprintf(h->last_kernel, sizeof(h->last_kernel), "k_search_lstm<%d, %s, %d>", h->maxa, P.philox ? "true" : "false", ks);
+    else snprintf(h->last_kernel, sizeof(h->last_kernel), P.philox ? "k_search_lstm<%d, true>" : "k_search_lstm<%d>", h->maxa);
+    return search_launched(h);
 }
 
 }  // namespace

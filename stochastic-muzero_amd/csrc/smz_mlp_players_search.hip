@@ -192,7 +192,7 @@ int players_search_tpw(int B) {
 
 int search_mlp_players_launch(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, int train,
                               ActOut act, const double *pow_table_host, smz_stream stream) {
-    if (h && h->large_actions) return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp_players: large-action handles search step-wise only%s");
+    if (h && h->large_actions) return refuse_large_actions("smz_search_mlp_players");
     if (!h || !desc || !weights_dev || !obs_dev) return fail(SMZ_ERR_INVALID, "smz_search_mlp_players: null argument%s");
     if (h->P.n_cycle <= 1)
         return fail(SMZ_ERR_INVALID, "smz_search_mlp_players: a one-player handle (smz_set_players with more than one cycle entry selects this kernel): use smz_search_mlp%s");
@@ -205,8 +205,7 @@ int search_mlp_players_launch(smz_handle *h, const smz_mlp_desc *desc, const flo
     }
     if (desc->A != h->P.A || desc->S != h->P.S)
         return fail(SMZ_ERR_INVALID, "smz_search_mlp_players: network dimensions differ from the handle's%s");
-    if (train && h->cfg.num_simulations > 0 && !(h->cfg.root_dirichlet_alpha > 0))
-        return fail(SMZ_ERR_INVALID, "root_dirichlet_alpha must be > 0 to draw noise (numpy raises ValueError)%s");
+    if (const int rc = check_dirichlet_alpha(h, train)) return rc;
     DeviceGuard guard(h->cfg.device);
     Params P = h->P;
     const int tpw = players_search_tpw(P.B);
@@ -215,46 +214,28 @@ int search_mlp_players_launch(smz_handle *h, const smz_mlp_desc *desc, const flo
     if (ml.total * (long long)sizeof(float) > 160 * 1024)
         return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp_players: working set exceeds the 160 KB LDS of a CU%s");
     const size_t lds = (size_t)ml.total * sizeof(float);
-    if (act.action && pow_table_host && act.temperature >= 0.3) {       // as smz_act: the power table of this temperature
-        if (!h->pow_valid || h->pow_T != act.temperature) {
-            HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-            HIP_TRY(hipMemcpy(h->d_pow, pow_table_host, ((size_t)h->cfg.num_simulations + 1) * sizeof(double), hipMemcpyHostToDevice));
-            h->pow_T = act.temperature;
-            h->pow_valid = true;
-        }
-        P.pow_table = h->d_pow;
-    }
+    if (act.action && use_pow_table(h, P, act.temperature, pow_table_host, stream) != SMZ_OK) return SMZ_ERR_HIP;
     P.tpw = tpw;
-    const int blocks = (P.B + kPlayersWaves * tpw - 1) / (kPlayersWaves * tpw);
-#define SMZ_LAUNCH_PS(MA) { if (h->K == 2) SMZ_LAUNCH_PS1(MA, 2) else SMZ_LAUNCH_PS1(MA, 0) }
-#define SMZ_LAUNCH_PS1(MA, KK) { if (P.philox) SMZ_LAUNCH_PS2(MA, KK, true) else SMZ_LAUNCH_PS2(MA, KK, false) }
+    const int blocks = (P.B + kPlayersWaves * tpw - 1) / (kPlayersWaves * tpw), ks = h->K == 2 ? 2 : 0;
+#define SMZ_LAUNCH_PS(MA) (ks ? SMZ_LAUNCH_PS1(MA, 2) : SMZ_LAUNCH_PS1(MA, 0))
+#define SMZ_LAUNCH_PS1(MA, KK) (P.philox ? SMZ_LAUNCH_PS2(MA, KK, true) : SMZ_LAUNCH_PS2(MA, KK, false))
 #define SMZ_LAUNCH_PS2(MA, KK, PX)                                                                                     \
-    {                                                                                                                  \
-        static size_t granted_dev[64] = {};                                                                            \
-        size_t &granted = granted_dev[h->cfg.device & 63];                                                             \
-        if (lds > granted) {                                                                                           \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_mlp_players<MA, KK, PX>),                  \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)               \
-                return fail(SMZ_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS) failed%s");                             \
-            granted = lds;                                                                                             \
-        }                                                                                                              \
-        hipLaunchKernelGGL((k_search_mlp_players<MA, KK, PX>), dim3(blocks), dim3(kPlayersWaves * kWave), lds,         \
-                           (hipStream_t)stream, P, *desc, weights_dev, obs_dev, train, act);                           \
-        snprintf(h->last_kernel, sizeof(h->last_kernel), "k_search_mlp_players<%d, %d, %s>", MA, KK, PX ? "true" : "false"); \
-    }
+    launch_with_lds<k_search_mlp_players<MA, KK, PX>>(h, blocks, kPlayersWaves * kWave, lds, stream, P, *desc, weights_dev, obs_dev, \
+                                                      train, act)
+    int rc;
     switch (h->maxa) {
-        case 2: SMZ_LAUNCH_PS(2) break;
-        case 4: SMZ_LAUNCH_PS(4) break;
-        case 8: SMZ_LAUNCH_PS(8) break;
-        case 16: SMZ_LAUNCH_PS(16) break;
-        default: SMZ_LAUNCH_PS(32) break;
+        case 2: rc = SMZ_LAUNCH_PS(2); break;
+        case 4: rc = SMZ_LAUNCH_PS(4); break;
+        case 8: rc = SMZ_LAUNCH_PS(8); break;
+        case 16: rc = SMZ_LAUNCH_PS(16); break;
+        default: rc = SMZ_LAUNCH_PS(32); break;
     }
 #undef SMZ_LAUNCH_PS
 #undef SMZ_LAUNCH_PS1
 #undef SMZ_LAUNCH_PS2
-    h->root_ready = true;
-    h->selected = false;
-    return launch_check();
+    if (rc != SMZ_OK) return rc;
+    snprintf(h->last_kernel, sizeof(h->last_kernel), "k_search_mlp_players<%d, %d, %s>", h->maxa, ks, P.philox ? "true" : "false");
+    return search_launched(h);
 }
 
 }  // namespace

@@ -262,9 +262,9 @@ int wide_search_tpw(int B) {
 
 int search_mlp_wide_launch(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *hidden0_dev,
                            const float *policy0_dev, int train, ActOut act, const double *pow_table_host, smz_stream stream) {
-    if (h && h->large_actions) return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp_wide: large-action handles search step-wise only%s");
+    if (h && h->large_actions) return refuse_large_actions("smz_search_mlp_wide");
     if (!h || !desc || !weights_dev || !hidden0_dev || !policy0_dev) return fail(SMZ_ERR_INVALID, "smz_search_mlp_wide: null argument%s");
-    if (h->P.n_cycle > 1) return fail(SMZ_ERR_INVALID, "smz_search_mlp_wide: multi-player handles search step-wise only%s");
+    if (h->P.n_cycle > 1) return refuse_multi_player("smz_search_mlp_wide");
     {
         smz_mlp_desc t = *desc;
         if (smz_mlp_layout_wide(&t) != SMZ_OK || t.total_floats != desc->total_floats || desc->OP != kWideOP)
@@ -274,8 +274,7 @@ int search_mlp_wide_launch(smz_handle *h, const smz_mlp_desc *desc, const float 
         return fail(SMZ_ERR_INVALID, "smz_search_mlp_wide: network dimensions differ from the handle's%s");
     if (h->maxa > 4 || h->P.A != h->maxa)
         return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp_wide: outside the single-launch kernel's limits (2 or 4 actions): use the step-wise entry points%s");
-    if (train && h->cfg.num_simulations > 0 && !(h->cfg.root_dirichlet_alpha > 0))
-        return fail(SMZ_ERR_INVALID, "root_dirichlet_alpha must be > 0 to draw noise (numpy raises ValueError)%s");
+    if (const int rc = check_dirichlet_alpha(h, train)) return rc;
     DeviceGuard guard(h->cfg.device);
     Params P = h->P;
     const int tpw = wide_search_tpw(P.B);
@@ -283,42 +282,21 @@ int search_mlp_wide_launch(smz_handle *h, const smz_mlp_desc *desc, const float 
     const WideLds ml = wide_lds(P.A, P.sims, tpw);
     const size_t lds = (size_t)ml.total * sizeof(float);
     if (lds > 160 * 1024) return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp_wide: working set exceeds the 160 KB LDS of a CU%s");
-    if (act.action && pow_table_host && act.temperature >= 0.3) {
-        if (!h->pow_valid || h->pow_T != act.temperature) {
-            HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-            HIP_TRY(hipMemcpy(h->d_pow, pow_table_host, ((size_t)h->cfg.num_simulations + 1) * sizeof(double), hipMemcpyHostToDevice));
-            h->pow_T = act.temperature;
-            h->pow_valid = true;
-        }
-        P.pow_table = h->d_pow;
-    }
+    if (act.action && use_pow_table(h, P, act.temperature, pow_table_host, stream) != SMZ_OK) return SMZ_ERR_HIP;
     P.tpw = tpw;
-    const int blocks = (P.B + kSearchWaves * tpw - 1) / (kSearchWaves * tpw);
-#define SMZ_LAUNCH_WS(MA) { if (h->K == 2) SMZ_LAUNCH_WS1(MA, 2) else SMZ_LAUNCH_WS1(MA, 0) }
-#define SMZ_LAUNCH_WS1(MA, KK) { if (P.philox) SMZ_LAUNCH_WS2(MA, true, KK) else SMZ_LAUNCH_WS2(MA, false, KK) }
-#define SMZ_LAUNCH_WS2(MA, PX, KK)                                                                                     \
-    {                                                                                                                  \
-        static size_t granted_dev[64] = {};                                                                            \
-        size_t &granted = granted_dev[h->cfg.device & 63];                                                             \
-        if (lds > granted) {                                                                                           \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_mlp_wide<MA, PX, KK>),                     \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)               \
-                return fail(SMZ_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS) failed%s");                             \
-            granted = lds;                                                                                             \
-        }                                                                                                              \
-        hipLaunchKernelGGL((k_search_mlp_wide<MA, PX, KK>), dim3(blocks), dim3(kSearchWaves * kWave), lds, (hipStream_t)stream, P, \
-                           *desc, weights_dev, hidden0_dev, policy0_dev, train, act);                                  \
-        if (KK) snprintf(h->last_kernel, sizeof(h->last_kernel), "k_search_mlp_wide<%d, %s, %d>", MA, PX ? "true" : "false", KK); \
-        else snprintf(h->last_kernel, sizeof(h->last_kernel), PX ? "k_search_mlp_wide<%d, true>" : "k_search_mlp_wide<%d>", MA); \
-    }
-    if (h->maxa == 2) SMZ_LAUNCH_WS(2)
-    else SMZ_LAUNCH_WS(4)
+    const int blocks = (P.B + kSearchWaves * tpw - 1) / (kSearchWaves * tpw), ks = h->K == 2 ? 2 : 0;
+#define SMZ_LAUNCH_WS(MA, KK) (P.philox ? SMZ_LAUNCH_WS1(MA, true, KK) : SMZ_LAUNCH_WS1(MA, false, KK))
+#define SMZ_LAUNCH_WS1(MA, PX, KK)                                                                                     \
+    launch_with_lds<k_search_mlp_wide<MA, PX, KK>>(h, blocks, kSearchWaves * kWave, lds, stream, P, *desc, weights_dev, hidden0_dev, \
+                                                   policy0_dev, train, act)
+    const int rc = h->maxa == 2 ? (ks ? SMZ_LAUNCH_WS(2, 2) : SMZ_LAUNCH_WS(2, 0)) : (ks ? SMZ_LAUNCH_WS(4, 2) : SMZ_LAUNCH_WS(4, 0));
 #undef SMZ_LAUNCH_WS
 #undef SMZ_LAUNCH_WS1
-#undef SMZ_LAUNCH_WS2
-    h->root_ready = true;
-    h->selected = false;
-    return launch_check();
+    if (rc != SMZ_OK) return rc;
+    // (the name as rocprofv3 prints it: without the defaulted arguments)
+    if (ks) snprintf(h->last_kernel, sizeof(h->last_kernel), "k_search_mlp_wide<%d, %s, %d>", h->maxa, P.philox ? "true" : "false", ks);
+    else snprintf(h->last_kernel, sizeof(h->last_kernel), P.philox ? "k_search_mlp_wide<%d, true>" : "k_search_mlp_wide<%d>", h->maxa);
+    return search_launched(h);
 }
 
 }  // namespace

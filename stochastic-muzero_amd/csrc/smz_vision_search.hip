@@ -631,9 +631,9 @@ __global__ void __launch_bounds__(kVW *kWave) SMZ_VISION_OCC k_search_vision(Par
 
 int search_vision_launch(smz_handle *h, const smz_vision_desc *desc, const float *weights_dev, const float *hidden0_dev,
                          const float *policy0_dev, int train, ActOut act, const double *pow_table_host, smz_stream stream) {
-    if (h && h->large_actions) return fail(SMZ_ERR_TOO_LARGE, "smz_search_vision: large-action handles search step-wise only%s");
+    if (h && h->large_actions) return refuse_large_actions("smz_search_vision");
     if (!h || !desc || !weights_dev || !hidden0_dev || !policy0_dev) return fail(SMZ_ERR_INVALID, "smz_search_vision: null argument%s");
-    if (h->P.n_cycle > 1) return fail(SMZ_ERR_INVALID, "smz_search_vision: multi-player handles search step-wise only%s");
+    if (h->P.n_cycle > 1) return refuse_multi_player("smz_search_vision");
     smz_vision_desc t = *desc;
     if (smz_vision_layout(&t) != SMZ_OK || t.total_floats != desc->total_floats)
         return fail(SMZ_ERR_INVALID, "smz_search_vision: descriptor does not describe a vision_model weight buffer%s");
@@ -642,49 +642,29 @@ int search_vision_launch(smz_handle *h, const smz_vision_desc *desc, const float
     if (h->K != 2 || h->P.A > 4 || desc->S > 32 || desc->H > 64)
         return fail(SMZ_ERR_TOO_LARGE, "smz_search_vision: outside the single-launch kernel's limits (K = 2, A <= 4, S <= 32, H <= 64): "
                                        "use the step-wise entry points%s");
-    if (train && h->cfg.num_simulations > 0 && !(h->cfg.root_dirichlet_alpha > 0))
-        return fail(SMZ_ERR_INVALID, "root_dirichlet_alpha must be > 0 to draw noise (numpy raises ValueError)%s");
+    if (const int rc = check_dirichlet_alpha(h, train)) return rc;
     DeviceGuard guard(h->cfg.device);
     Params P = h->P;
-    if (act.action && pow_table_host && act.temperature >= 0.3) {
-        if (!h->pow_valid || h->pow_T != act.temperature) {
-            HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-            HIP_TRY(hipMemcpy(h->d_pow, pow_table_host, ((size_t)h->cfg.num_simulations + 1) * sizeof(double), hipMemcpyHostToDevice));
-            h->pow_T = act.temperature;
-            h->pow_valid = true;
-        }
-        P.pow_table = h->d_pow;
-    }
     P.tpw = 1;
     const VisLds ml = vis_lds(P, P.A);
     const size_t lds = (size_t)ml.total * sizeof(float);
     if (lds > 160 * 1024) return fail(SMZ_ERR_TOO_LARGE, "smz_search_vision: working set exceeds the 160 KB LDS of a CU%s");
+    if (act.action && use_pow_table(h, P, act.temperature, pow_table_host, stream) != SMZ_OK) return SMZ_ERR_HIP;
     const int blocks = (P.B + kVW - 1) / kVW;
-#define SMZ_LAUNCH_VS(MA, EQ) { if (P.philox) SMZ_LAUNCH_VS2(MA, EQ, true) else SMZ_LAUNCH_VS2(MA, EQ, false) }
+    const bool eq = P.A == h->maxa;                  // (A <= 4: the bucket is 2 or 4)
+#define SMZ_LAUNCH_VS(MA, EQ) (P.philox ? SMZ_LAUNCH_VS2(MA, EQ, true) : SMZ_LAUNCH_VS2(MA, EQ, false))
 #define SMZ_LAUNCH_VS2(MA, EQ, PX)                                                                                     \
-    {                                                                                                                  \
-        static size_t granted_dev[64] = {};                                                                            \
-        size_t &granted = granted_dev[h->cfg.device & 63];                                                             \
-        if (lds > granted) {                                                                                           \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_search_vision<MA, EQ, PX>),                       \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)               \
-                return fail(SMZ_ERR_HIP, "hipFuncSetAttribute(max dynamic LDS) failed%s");                             \
-            granted = lds;                                                                                             \
-        }                                                                                                              \
-        hipLaunchKernelGGL((k_search_vision<MA, EQ, PX>), dim3(blocks), dim3(kVW * kWave), lds, (hipStream_t)stream, P, \
-                           *desc, weights_dev, hidden0_dev, policy0_dev, train, act);                                  \
-        snprintf(h->last_kernel, sizeof(h->last_kernel), PX ? "k_search_vision<%d, %s, true>" : "k_search_vision<%d, %s>", MA, \
-                 EQ ? "true" : "false");                                                                               \
-    }
-    if (h->maxa == 2 && P.A == 2) SMZ_LAUNCH_VS(2, true)
-    else if (h->maxa == 2) SMZ_LAUNCH_VS(2, false)
-    else if (P.A == 4) SMZ_LAUNCH_VS(4, true)
-    else SMZ_LAUNCH_VS(4, false)
+    launch_with_lds<k_search_vision<MA, EQ, PX>>(h, blocks, kVW * kWave, lds, stream, P, *desc, weights_dev, hidden0_dev,  \
+                                                 policy0_dev, train, act)
+    const int rc = h->maxa == 2 ? (eq ? SMZ_LAUNCH_VS(2, true) : SMZ_LAUNCH_VS(2, false))
+                                : (eq ? SMZ_LAUNCH_VS(4, true) : SMZ_LAUNCH_VS(4, false));
 #undef SMZ_LAUNCH_VS
 #undef SMZ_LAUNCH_VS2
-    h->root_ready = true;
-    h->selected = false;
-    return launch_check();
+    if (rc != SMZ_OK) return rc;
+    // (the name as rocprofv3 prints it: without the defaulted argument)
+    snprintf(h->last_kernel, sizeof(h->last_kernel), P.philox ? "k_search_vision<%d, %s, true>" : "k_search_vision<%d, %s>", h->maxa,
+             eq ? "true" : "false");
+    return search_launched(h);
 }
 
 }  // namespace

@@ -220,113 +220,70 @@ class SearchEngine:
             tab = self._pow_tables[temperature] = pow_table(temperature, self.sims + 1)
         return tab
 
+    def _launch_search(self, name, desc, weights, inputs, train, act_temperature):
+        """The call every search_* method makes: lib.<name>, or lib.<name>_act with the power table of `act_temperature` and the
+        engine's act buffers; `inputs` are the tensors between the weights and `train`."""
+        self._act_done = None
+        self.env_stepped = False
+        args = [self.h, C.byref(desc), _ptr(weights), *(_ptr(t) for t in inputs), int(bool(train))]
+        if act_temperature is None:
+            _lib.check(getattr(self.lib, name)(*args, self._stream()))
+            return
+        T = float(act_temperature)
+        tab = self._pow_table(T)
+        _lib.check(getattr(self.lib, name + "_act")(*args, T, None if tab is None else tab.ctypes.data_as(C.c_void_p),
+                                                    _ptr(self.action), _ptr(self.policy), _ptr(self.child_visits),
+                                                    _ptr(self.root_value), self._stream()))
+        self._act_done = T
+
+    def _obs(self, obs):
+        assert obs.dtype == torch.float32 and obs.is_contiguous() and obs.shape[0] == self.B
+        return (obs,)
+
+    def _root(self, hidden0, policy0):
+        return self._f32(hidden0.reshape(self.B, -1), (self.B, self.S)), self._f32(policy0, (self.B, self.A))
+
     def search_mlp(self, mlp_desc, weights, obs, train=True, act_temperature=None, env_step=None):
         """Whole search (root + num_simulations rounds) in one launch with LDS-resident mlp_model heads.  With
         `act_temperature` the action selection of act() runs in the tail of the same launch; the next act() call with
         that temperature returns its outputs without launching anything.  `env_step` (a _lib.CartPoleEnv whose obs_dev is
         `obs`; needs act_temperature): the built-in env's step + trajectory record run in the tail too
         (smz_search_mlp_act_cartpole) -- one launch per env step."""
-        assert obs.dtype == torch.float32 and obs.is_contiguous() and obs.shape[0] == self.B
+        if env_step is None:
+            return self._launch_search("smz_search_mlp", mlp_desc, weights, self._obs(obs), train, act_temperature)
+        self._obs(obs)
         self._act_done = None
         self.env_stepped = False
-        if env_step is not None:
-            assert act_temperature is not None and env_step.obs_dev == obs.data_ptr()
-            T = float(act_temperature)
-            tab = self._pow_table(T)
-            _lib.check(self.lib.smz_search_mlp_act_cartpole(self.h, C.byref(mlp_desc), _ptr(weights), int(bool(train)), T,
-                                                            None if tab is None else tab.ctypes.data_as(C.c_void_p),
-                                                            _ptr(self.action), _ptr(self.policy), _ptr(self.child_visits),
-                                                            _ptr(self.root_value), C.byref(env_step), self._stream()))
-            self._act_done = T
-            self.env_stepped = True
-            return
-        if act_temperature is None:
-            _lib.check(self.lib.smz_search_mlp(self.h, C.byref(mlp_desc), _ptr(weights), _ptr(obs), int(bool(train)),
-                                               self._stream()))
-            return
+        assert act_temperature is not None and env_step.obs_dev == obs.data_ptr()
         T = float(act_temperature)
         tab = self._pow_table(T)
-        _lib.check(self.lib.smz_search_mlp_act(self.h, C.byref(mlp_desc), _ptr(weights), _ptr(obs), int(bool(train)), T,
-                                               None if tab is None else tab.ctypes.data_as(C.c_void_p), _ptr(self.action),
-                                               _ptr(self.policy), _ptr(self.child_visits), _ptr(self.root_value),
-                                               self._stream()))
+        _lib.check(self.lib.smz_search_mlp_act_cartpole(self.h, C.byref(mlp_desc), _ptr(weights), int(bool(train)), T,
+                                                        None if tab is None else tab.ctypes.data_as(C.c_void_p),
+                                                        _ptr(self.action), _ptr(self.policy), _ptr(self.child_visits),
+                                                        _ptr(self.root_value), C.byref(env_step), self._stream()))
         self._act_done = T
+        self.env_stepped = True
 
     def search_vision(self, vision_desc, weights, hidden0, policy0, train=True, act_temperature=None):
         """Whole search in one launch for `vision_model` heads (smz_search_vision): hidden0 [B,147] / policy0 [B,A] are
         smz_vision_initial's outputs.  `act_temperature` as in search_mlp."""
-        hidden0 = self._f32(hidden0.reshape(self.B, -1), (self.B, self.S))
-        policy0 = self._f32(policy0, (self.B, self.A))
-        self._act_done = None
-        self.env_stepped = False
-        if act_temperature is None:
-            _lib.check(self.lib.smz_search_vision(self.h, C.byref(vision_desc), _ptr(weights), _ptr(hidden0), _ptr(policy0),
-                                                  int(bool(train)), self._stream()))
-            return
-        T = float(act_temperature)
-        tab = self._pow_table(T)
-        _lib.check(self.lib.smz_search_vision_act(self.h, C.byref(vision_desc), _ptr(weights), _ptr(hidden0), _ptr(policy0),
-                                                  int(bool(train)), T, None if tab is None else tab.ctypes.data_as(C.c_void_p),
-                                                  _ptr(self.action), _ptr(self.policy), _ptr(self.child_visits),
-                                                  _ptr(self.root_value), self._stream()))
-        self._act_done = T
+        self._launch_search("smz_search_vision", vision_desc, weights, self._root(hidden0, policy0), train, act_temperature)
 
     def search_lstm(self, lstm_desc, weights, hidden0, policy0, train=True, act_temperature=None):
         """Whole search in one launch for `lstm_model` heads (smz_search_lstm): hidden0 [B,S] / policy0 [B,A] are
         smz_lstm_initial's outputs.  `act_temperature` as in search_mlp."""
-        hidden0 = self._f32(hidden0.reshape(self.B, -1), (self.B, self.S))
-        policy0 = self._f32(policy0, (self.B, self.A))
-        self._act_done = None
-        self.env_stepped = False
-        if act_temperature is None:
-            _lib.check(self.lib.smz_search_lstm(self.h, C.byref(lstm_desc), _ptr(weights), _ptr(hidden0), _ptr(policy0),
-                                                int(bool(train)), self._stream()))
-            return
-        T = float(act_temperature)
-        tab = self._pow_table(T)
-        _lib.check(self.lib.smz_search_lstm_act(self.h, C.byref(lstm_desc), _ptr(weights), _ptr(hidden0), _ptr(policy0),
-                                                int(bool(train)), T, None if tab is None else tab.ctypes.data_as(C.c_void_p),
-                                                _ptr(self.action), _ptr(self.policy), _ptr(self.child_visits),
-                                                _ptr(self.root_value), self._stream()))
-        self._act_done = T
+        self._launch_search("smz_search_lstm", lstm_desc, weights, self._root(hidden0, policy0), train, act_temperature)
 
     def search_mlp_wide(self, wide_desc, packed, hidden0, policy0, train=True, act_temperature=None):
         """Whole search in one launch for the wide `mlp_model` heads (smz_search_mlp_wide; HipMlpTileHeads.wide_desc / .packed):
         hidden0 [B,S] / policy0 [B,A] are the outputs of the heads' initial().  `act_temperature` as in search_mlp."""
-        hidden0 = self._f32(hidden0.reshape(self.B, -1), (self.B, self.S))
-        policy0 = self._f32(policy0, (self.B, self.A))
-        self._act_done = None
-        self.env_stepped = False
-        if act_temperature is None:
-            _lib.check(self.lib.smz_search_mlp_wide(self.h, C.byref(wide_desc), _ptr(packed), _ptr(hidden0), _ptr(policy0),
-                                                    int(bool(train)), self._stream()))
-            return
-        T = float(act_temperature)
-        tab = self._pow_table(T)
-        _lib.check(self.lib.smz_search_mlp_wide_act(self.h, C.byref(wide_desc), _ptr(packed), _ptr(hidden0), _ptr(policy0),
-                                                    int(bool(train)), T, None if tab is None else tab.ctypes.data_as(C.c_void_p),
-                                                    _ptr(self.action), _ptr(self.policy), _ptr(self.child_visits),
-                                                    _ptr(self.root_value), self._stream()))
-        self._act_done = T
+        self._launch_search("smz_search_mlp_wide", wide_desc, packed, self._root(hidden0, policy0), train, act_temperature)
 
     def search_mlp_players(self, mlp_desc, weights, obs, train=True, act_temperature=None):
         """Whole search in one launch for a multi-player engine (set_players with more than one cycle entry) and LDS-resident
         mlp_model heads (smz_search_mlp_players).  The root players are what `self.root_player` holds (set_root_player).
         `act_temperature` as in search_mlp."""
-        assert obs.dtype == torch.float32 and obs.is_contiguous() and obs.shape[0] == self.B
-        self._act_done = None
-        self.env_stepped = False
-        if act_temperature is None:
-            _lib.check(self.lib.smz_search_mlp_players(self.h, C.byref(mlp_desc), _ptr(weights), _ptr(obs), int(bool(train)),
-                                                       self._stream()))
-            return
-        T = float(act_temperature)
-        tab = self._pow_table(T)
-        _lib.check(self.lib.smz_search_mlp_players_act(self.h, C.byref(mlp_desc), _ptr(weights), _ptr(obs), int(bool(train)), T,
-                                                       None if tab is None else tab.ctypes.data_as(C.c_void_p), _ptr(self.action),
-                                                       _ptr(self.policy), _ptr(self.child_visits), _ptr(self.root_value),
-                                                       self._stream()))
-        self._act_done = T
+        self._launch_search("smz_search_mlp_players", mlp_desc, weights, self._obs(obs), train, act_temperature)
 
     def root_stats(self):
         _lib.check(self.lib.smz_root_stats(self.h, _ptr(self.visits), _ptr(self.priors), _ptr(self.root_value),

@@ -201,9 +201,7 @@ class BatchedMCTS(_Hyper):
     def _search(self, obs, heads, train):
         hidden, policy = heads.initial(obs)
         eng = self._ensure_engine(policy.shape[1], hidden.shape[1])
-        if getattr(self, "_pending_seed", None) is not None:
-            eng.seed(self._pending_seed)
-            self._pending_seed = None
+        self._seed_pending(eng)
         if not torch.cuda.is_current_stream_capturing():
             self._stage_to_play(eng)                 # (a captured graph reads the buffer staged before its replay)
         eng.root_init(hidden, policy, train=train)
@@ -228,9 +226,7 @@ class BatchedMCTS(_Hyper):
         self._static_obs = observations.clone()
         hidden, policy = heads.initial(self._static_obs)            # learns A and S; draws nothing
         eng = self._ensure_engine(policy.shape[1], hidden.shape[1])
-        if getattr(self, "_pending_seed", None) is not None:
-            eng.seed(self._pending_seed)
-            self._pending_seed = None
+        self._seed_pending(eng)
         # One throw-away search warms the allocator / hipBLASLt on a side stream (as graph capture requires);
         # the per-tree random streams are snapshotted around it so tree i still is np.random.seed(seed_i).
         eng.snapshot_rng()
@@ -270,108 +266,77 @@ class BatchedMCTS(_Hyper):
         if self.n_cycle > 1:
             eng.set_root_player(0 if self._to_play is None else self._to_play)
 
+    def _seed_pending(self, eng):
+        """Hands a seed() given before the engine existed to the engine, once."""
+        if getattr(self, "_pending_seed", None) is not None:
+            eng.seed(self._pending_seed)
+            self._pending_seed = None
+
+    def _try_single(self, eng, search, warning):
+        """One single-launch search: True if it ran.  Only SMZ_ERR_TOO_LARGE ("outside this kernel's limits for this geometry")
+        selects the step-wise path, and only before any single launch has succeeded: once, said aloud with `warning(err)`.  A HIP
+        error, a bad descriptor or a bad observation tensor is a failure, not a slow path."""
+        self._seed_pending(eng)
+        try:
+            search()
+        except _lib.SmzError as err:
+            if err.code != _lib.SMZ_ERR_TOO_LARGE or self._single is True:
+                raise
+            self._single = False
+            warnings.warn(warning(err))
+            return False
+        self._single = True
+        return True
+
     def _run(self, observations, heads, train, act_temperature, env_step, record_obs):
         self._recorded = False
+        # (single_launch_max_trees: where the step-wise kernels overtake the single launch)
+        single = self.single_launch and self._single is not False and self.num_trees <= self.single_launch_max_trees
+        desc = getattr(heads, "desc", None)
+        kw = dict(train=train, act_temperature=act_temperature)
+
+        def outside(what):
+            return lambda err: f"single-launch {what} is outside its limits for this configuration ({err}): using the step-wise kernels"
+
+        def rooted(**record):
+            hidden, policy = heads.initial(observations, **record)
+            return hidden, policy, self._ensure_engine(policy.shape[1], hidden.shape[1])
+
         if self.n_cycle > 1:
             # the multi-player backup: the step-wise kernels, or (opt-in, HipMlpHeads) the single launch built for these handles;
             # every other single launch refuses them
-            if (self.players_single_launch and self.single_launch and isinstance(getattr(heads, "desc", None), _lib.MlpDesc)
-                    and int(heads.A) <= _lib.MAX_ACTIONS and self.num_trees <= self.single_launch_max_trees
-                    and self._single is not False):
+            if single and self.players_single_launch and isinstance(desc, _lib.MlpDesc) and int(heads.A) <= _lib.MAX_ACTIONS:
                 eng = self._ensure_engine(heads.A, heads.S)
-                if getattr(self, "_pending_seed", None) is not None:
-                    eng.seed(self._pending_seed)
-                    self._pending_seed = None
                 self._stage_to_play(eng)
-                try:
-                    eng.search_mlp_players(heads.desc, heads.weights, observations, train=train, act_temperature=act_temperature)
-                    self._single = True
+                if self._try_single(eng, lambda: eng.search_mlp_players(heads.desc, heads.weights, observations, **kw),
+                                    outside("multi-player search")):
                     return eng
-                except _lib.SmzError as err:
-                    if err.code != _lib.SMZ_ERR_TOO_LARGE or self._single is True:
-                        raise
-                    self._single = False
-                    warnings.warn("single-launch multi-player search is outside its limits for this configuration "
-                                  f"({err}): using the step-wise kernels")
-            return self._run_stepwise(observations, heads, train)
-        if int(getattr(heads, "A", 0)) > _lib.MAX_ACTIONS:
-            # more actions than the per-lane kernels take: the wave-per-tree step-wise kernels (no single launch)
-            return self._run_stepwise(observations, heads, train)
-        # (single_launch_max_trees: where the step-wise kernels overtake the single launch)
-        if (self.single_launch and isinstance(getattr(heads, "desc", None), _lib.MlpDesc) and self._single is not False
-                and self.num_trees <= self.single_launch_max_trees):
+        elif int(getattr(heads, "A", 0)) > _lib.MAX_ACTIONS:
+            pass       # more actions than the per-lane kernels take: the wave-per-tree step-wise kernels (no single launch)
+        elif single and isinstance(desc, _lib.MlpDesc):
             eng = self._ensure_engine(heads.A, heads.S)
-            if getattr(self, "_pending_seed", None) is not None:
-                eng.seed(self._pending_seed)
-                self._pending_seed = None
-            try:
-                eng.search_mlp(heads.desc, heads.weights, observations, train=train, act_temperature=act_temperature,
-                               env_step=env_step if act_temperature is not None else None)
-                self._single = True
+            if self._try_single(eng, lambda: eng.search_mlp(heads.desc, heads.weights, observations,
+                                                            env_step=env_step if act_temperature is not None else None, **kw),
+                                lambda err: "single-launch search does not fit in LDS for this batch geometry "
+                                            f"({self.num_trees} trees x {self.num_simulations} simulations): using the step-wise kernels"):
                 return eng
-            except _lib.SmzError as err:
-                # only "the working set does not fit a CU's LDS for this geometry" selects the step-wise path (once,
-                # said aloud); a HIP error, a bad descriptor or a bad observation tensor is a failure, not a slow path
-                if err.code != _lib.SMZ_ERR_TOO_LARGE or self._single is True:
-                    raise
-                self._single = False
-                warnings.warn("single-launch search does not fit in LDS for this batch geometry "
-                              f"({self.num_trees} trees x {self.num_simulations} simulations): using the step-wise kernels")
-        # vision_model heads: representation per frame (its own launch), then the whole search in one launch
-        if (self.single_launch and isinstance(getattr(heads, "desc", None), _lib.VisionDesc) and self._single is not False
-                and self.num_trees <= self.single_launch_max_trees):
-            hidden, policy = heads.initial(observations, **({} if record_obs is None else dict(record=record_obs)))
+        elif single and isinstance(desc, _lib.VisionDesc):
+            # vision_model heads: representation per frame (its own launch), then the whole search in one launch
+            hidden, policy, eng = rooted(**({} if record_obs is None else dict(record=record_obs)))
             self._recorded = record_obs is not None
-            eng = self._ensure_engine(policy.shape[1], hidden.shape[1])
-            if getattr(self, "_pending_seed", None) is not None:
-                eng.seed(self._pending_seed)
-                self._pending_seed = None
-            try:
-                eng.search_vision(heads.desc, heads.weights, hidden, policy, train=train, act_temperature=act_temperature)
-                self._single = True
+            if self._try_single(eng, lambda: eng.search_vision(heads.desc, heads.weights, hidden, policy, **kw), outside("vision search")):
                 return eng
-            except _lib.SmzError as err:
-                if err.code != _lib.SMZ_ERR_TOO_LARGE or self._single is True:
-                    raise
-                self._single = False
-                warnings.warn("single-launch vision search is outside its limits for this configuration "
-                              f"({err}): using the step-wise kernels")
-        # lstm_model heads, opt-in: representation + root policy (its own launch), then the whole search in one launch
-        if (self.single_launch and self.lstm_single_launch and isinstance(getattr(heads, "desc", None), _lib.LstmDesc)
-                and self._single is not False and self.num_trees <= self.single_launch_max_trees):
-            hidden, policy = heads.initial(observations)
-            eng = self._ensure_engine(policy.shape[1], hidden.shape[1])
-            if getattr(self, "_pending_seed", None) is not None:
-                eng.seed(self._pending_seed)
-                self._pending_seed = None
-            try:
-                eng.search_lstm(heads.desc, heads.weights, hidden, policy, train=train, act_temperature=act_temperature)
-                self._single = True
+        elif single and self.lstm_single_launch and isinstance(desc, _lib.LstmDesc):
+            # lstm_model heads, opt-in: representation + root policy (its own launch), then the whole search in one launch
+            hidden, policy, eng = rooted()
+            if self._try_single(eng, lambda: eng.search_lstm(heads.desc, heads.weights, hidden, policy, **kw), outside("lstm search")):
                 return eng
-            except _lib.SmzError as err:
-                if err.code != _lib.SMZ_ERR_TOO_LARGE or self._single is True:
-                    raise
-                self._single = False
-                warnings.warn("single-launch lstm search is outside its limits for this configuration "
-                              f"({err}): using the step-wise kernels")
-        # wide mlp_model heads, opt-in: root evaluation (torch GEMMs), then the whole search in one launch
-        if (self.single_launch and self.wide_single_launch and isinstance(getattr(heads, "wide_desc", None), _lib.MlpDesc)
-                and self._single is not False and self.num_trees <= self.single_launch_max_trees):
-            hidden, policy = heads.initial(observations)
-            eng = self._ensure_engine(policy.shape[1], hidden.shape[1])
-            if getattr(self, "_pending_seed", None) is not None:
-                eng.seed(self._pending_seed)
-                self._pending_seed = None
-            try:
-                eng.search_mlp_wide(heads.wide_desc, heads.packed, hidden, policy, train=train, act_temperature=act_temperature)
-                self._single = True
+        elif single and self.wide_single_launch and isinstance(getattr(heads, "wide_desc", None), _lib.MlpDesc):
+            # wide mlp_model heads, opt-in: root evaluation (torch GEMMs), then the whole search in one launch
+            hidden, policy, eng = rooted()
+            if self._try_single(eng, lambda: eng.search_mlp_wide(heads.wide_desc, heads.packed, hidden, policy, **kw),
+                                outside("wide mlp search")):
                 return eng
-            except _lib.SmzError as err:
-                if err.code != _lib.SMZ_ERR_TOO_LARGE or self._single is True:
-                    raise
-                self._single = False
-                warnings.warn("single-launch wide mlp search is outside its limits for this configuration "
-                              f"({err}): using the step-wise kernels")
         return self._run_stepwise(observations, heads, train)
 
     def _run_stepwise(self, observations, heads, train):

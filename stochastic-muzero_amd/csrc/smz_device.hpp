@@ -1,7 +1,7 @@
 // smz_device.hpp -- device-side building blocks of the gfx950 search kernels.
 //
 // Execution shape: one search tree per lane, 64 trees per wavefront.  The per-tree logic below is scalar code run
-// by one lane; the wave-cooperative parts (random-word staging, hidden-row moves) live in smz_kernels.hip.
+// by one lane; the wave-cooperative parts (random-word staging, hidden-row moves) live in smz_common.hpp.
 // The arithmetic follows, operation by operation and with the same float32/float64 roundings, the reference's
 // monte_carlo_tree_search.py and the numpy legacy RandomState it draws from.  This translation unit MUST be
 // compiled with -ffp-contract=off: a fused multiply-add would change roundings the reference performs separately.

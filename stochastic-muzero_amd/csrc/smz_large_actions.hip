@@ -17,8 +17,8 @@
 // compute each word where it is needed (philox_word).  Both consume exactly the per-lane kernels' words, in their order.
 //
 // Build: same flags as smz_kernels.hip (-ffp-contract=off: no fused multiply-add).
-#define SMZ_PART 5
-#include "smz_kernels.hip"
+#include "smz_common.hpp"
+#include "smz_handle.hpp"
 
 namespace {
 

@@ -11,8 +11,8 @@
 //     handle's hidden array; reward, value and policy go to the tree's slot in LDS for the next round's expansion.
 // Both paths draw the same random words and round alike: the searches are bit-identical (tests/test_gpu_lstm_search.py).
 // Limits (anything else runs step-wise): one player, 2 or 4 actions, at most 64 trees per wavefront, LDS map <= 160 KB.
-#define SMZ_PART 5
-#include "smz_kernels.hip"
+#include "smz_common.hpp"
+#include "smz_handle.hpp"
 #include "smz_lstm_device.hpp"
 
 using smz_lstm::kWavesPerWg;

@@ -23,7 +23,7 @@ extern __shared__ float4 smz_mlp_lds4[];
 
 // LDS map: [0, total_floats) the packed weights at their buffer offsets; then per-wave scratch
 // FASTD: the reference's shipped network shape (S 31, H 64, L 0) with the dimensions as compile-time constants
-// (layer loops unroll; see k_search_mlp in smz_kernels.hip); A stays a run-time value here.
+// (layer loops unroll; see k_search_mlp in smz_search_mlp.hpp); A stays a run-time value here.
 constexpr int kFastS = 31, kFastH = 64, kFastL = 0;
 template <int U, bool FASTD>
 __global__ void __launch_bounds__(512) k_mlp_recurrent(smz_mlp_desc d, const float *weights, const float *x,

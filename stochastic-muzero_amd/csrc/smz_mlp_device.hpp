@@ -1,5 +1,5 @@
 // smz_mlp_device.hpp -- device functions of the fused `mlp_model` heads (shared by the stand-alone head kernels in
-// smz_mlp.hip and by the whole-search kernel in smz_kernels.hip, so that both produce bit-identical network outputs).
+// smz_mlp.hip and by the whole-search kernel in smz_search_mlp.hpp, so that both produce bit-identical network outputs).
 //
 // Weights live in LDS in an input-major, 4-way interleaved layout (include/smz.h): lane o owns output neuron o and
 // fetches four consecutive input weights with one 16-byte LDS read, activations are broadcast 16-byte reads.  All
@@ -632,7 +632,7 @@ __device__ inline void stage_weights(float *lds, const float *weights, const int
 }
 
 constexpr int kRows = 1;   // rows per pass of the stand-alone heads kernel and of the generic search kernel (the specialised
-                           // search kernel evaluates its two leaves as one two-row pass: smz_kernels.hip)
+                           // search kernel evaluates its two leaves as one two-row pass: smz_search_mlp.hpp)
 
 // per-row LDS scratch: input vector | trunk activations | hidden state; a wave owns kRows of them
 __host__ __device__ inline int row_scratch_floats(const smz_mlp_desc &d) {

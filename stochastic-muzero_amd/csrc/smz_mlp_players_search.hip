@@ -24,8 +24,8 @@
 // wavefronts have a tree each before any takes a second one: tpw = ceil(B / 2048), at most 64.  SMZ_PLAYERS_SEARCH_TPW overrides
 // it (tests: a search does not depend on the geometry).
 // Limits (anything else runs step-wise): at most 32 actions, at most 64 trees per wavefront, LDS map <= 160 KB, no statistics.
-#define SMZ_PART 5
-#include "smz_kernels.hip"
+#include "smz_common.hpp"
+#include "smz_handle.hpp"
 
 using smz_mlp::lds_sync;
 using smz_mlp::up4;

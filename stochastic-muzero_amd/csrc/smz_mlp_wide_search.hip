@@ -17,8 +17,8 @@
 // Every wavefront of a workgroup reaches every barrier of every round: a wavefront without a searched tree stays in the loop
 // and takes tiles; only a workgroup none of whose trees is searched leaves, as a whole, before the rounds start.
 // Limits (anything else runs step-wise): one player, 2 or 4 actions, at most 64 trees per wavefront, LDS map <= 160 KB.
-#define SMZ_PART 5
-#include "smz_kernels.hip"
+#include "smz_common.hpp"
+#include "smz_handle.hpp"
 #include "smz_mlp_wide_device.hpp"
 
 using smz_mlp::kTileLeaves;

@@ -6,7 +6,7 @@
 // expansion that created it, so its lane can keep them in registers, the ancestors as masks in lane space.  Then
 //     good(b)    = the parent's pick equals b's slot                    (one bit test against the ballot of the picks)
 //     on path(b) = good(b) and every ancestor of b is good              (two mask tests against the ballots of good)
-// and the descent needs no dependent chain over the picks.  Plain integers only: the kernel (smz_kernels.hip) and a host test
+// and the descent needs no dependent chain over the picks.  Plain integers only: the kernel (smz_search_mlp.hpp) and a host test
 // (tests/test_select_masks.py) compile this same file.
 #pragma once
 #include <stdint.h>

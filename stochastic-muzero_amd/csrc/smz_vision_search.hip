@@ -22,8 +22,8 @@
 // (tests/test_gpu_end_to_end.py).
 // Limits of this kernel (anything else runs step-wise): maxium_action_sample == 2, A <= 4, S <= 32, H <= 64,
 // SMZ_RNG_MT19937_NUMPY, LDS working set <= 160 KB.
-#define SMZ_PART 5
-#include "smz_kernels.hip"
+#include "smz_common.hpp"
+#include "smz_handle.hpp"
 #include "smz_vision_device.hpp"
 
 using smz_mlp::decode_lanes;

@@ -77,7 +77,7 @@ def _kernel(lines, mangled_prefix):
 
 @pytest.fixture(scope="module")
 def part2_isa(tmp_path_factory):
-    return _isa(tmp_path_factory.mktemp("isa"), "smz_kernels.hip", ["-DSMZ_PART=2"])
+    return _isa(tmp_path_factory.mktemp("isa"), "smz_search.hip")
 
 
 @pytest.fixture(scope="module")

@@ -98,8 +98,8 @@ def test_players_search_kernels_exist_and_stay_within_the_generic_kernels_scratc
 
     Reported, not asserted (DESIGN.md 3.7 has the figures of this build): vector / scalar register counts and spill counts of every
     instantiation.  LDS is dynamic (sized on the host: players_lds)."""
-    jobs = {"players": ["smz_mlp_players_search.hip"], "part2": ["-DSMZ_PART=2", "smz_kernels.hip"],
-            "part4": ["-DSMZ_PART=4", "smz_kernels.hip"]}
+    jobs = {"players": ["smz_mlp_players_search.hip"], "search": ["smz_search.hip"],
+            "search_wide": ["smz_search_wide.hip"]}
     procs = {n: subprocess.Popen([HIPCC, *FLAGS, "-o", str(tmp_path / (n + ".s")), *args], cwd=CSRC, stdout=subprocess.DEVNULL,
                                  stderr=subprocess.PIPE, text=True) for n, args in jobs.items()}
     for n, p in procs.items():
@@ -107,7 +107,7 @@ def test_players_search_kernels_exist_and_stay_within_the_generic_kernels_scratc
         assert p.returncode == 0, (n, err[-2000:])
     new = _kernels((tmp_path / "players.s").read_text(), "k_search_mlp_players")
     generic = {}
-    for n in ("part2", "part4"):
+    for n in ("search", "search_wide"):
         generic.update(_kernels((tmp_path / (n + ".s")).read_text(), "12k_search_mlpI"))
     for n, f in sorted(new.items()):
         print(n, f)

@@ -143,12 +143,12 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-std=c++
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC) or os.environ.get("SMZ_SKIP_ISA_TESTS"), reason="needs hipcc")
-@pytest.mark.parametrize("part,fused", [(1, False), (3, True)])
-def test_multi_player_kernels_are_instantiated(tmp_path, part, fused):
+@pytest.mark.parametrize("source,fused", [("smz_kernels.hip", False), ("smz_fused.hip", True)])
+def test_multi_player_kernels_are_instantiated(tmp_path, source, fused):
     """Every dispatch of k_expand_backup has a k_expand_backup_mp twin (same template arguments), and the plain kernels
     keep their names."""
     out = tmp_path / "k.s"
-    r = subprocess.run([HIPCC, *FLAGS, f"-DSMZ_PART={part}", "-o", str(out), "smz_kernels.hip"], cwd=CSRC, capture_output=True,
+    r = subprocess.run([HIPCC, *FLAGS, "-o", str(out), source], cwd=CSRC, capture_output=True,
                        text=True, timeout=1800)
     assert r.returncode == 0, r.stderr[-2000:]
     names = {l.split(":")[0] for l in out.read_text().split("\n") if l.startswith("_Z") and l.split(";")[0].strip().endswith(":")}

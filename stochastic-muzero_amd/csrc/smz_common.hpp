@@ -525,6 +525,8 @@ __device__ inline void cartpole_env_step(const EnvStep &E, int e, int B, const i
     }
 }
 
+constexpr int kCus = 256;    // MI355X: the compute units the single-launch searches spread their workgroups over
+
 // (LDS maps of the single-launch searches: every part padded to 16 bytes)
 __host__ __device__ inline int r4(int x) { return (x + 3) & ~3; }
 

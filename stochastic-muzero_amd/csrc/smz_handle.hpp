@@ -101,6 +101,31 @@ int check_dirichlet_alpha(const smz_handle *h, int train) {
     return SMZ_OK;
 }
 
+// Trees per wavefront: every one of `waves` wavefronts (the launcher's workgroups per CU x kCus x wavefronts per workgroup) has a
+// tree before any takes a second one.  The environment variable `env_override` (nullptr: none) replaces the count (tests: a
+// search does not depend on the geometry).
+int single_launch_tpw(int B, int waves, const char *env_override) {
+    int tpw = (B + waves - 1) / waves;
+    if (const char *e = env_override ? getenv(env_override) : nullptr) {
+        const int v = atoi(e);
+        if (v >= 1) tpw = v;
+    }
+    return tpw < 1 ? 1 : tpw;
+}
+// The two size limits of a single-launch kernel: a tree per lane, and an LDS map of `lds_floats` floats on one CU.
+int check_single_launch_size(const char *who, int tpw, long long lds_floats) {
+    if (tpw > kWave) return fail(SMZ_ERR_TOO_LARGE, "%s: more than 64 trees per wavefront: use the step-wise entry points", who);
+    if (lds_floats * (long long)sizeof(float) > 160 * 1024)
+        return fail(SMZ_ERR_TOO_LARGE, "%s: working set exceeds the 160 KB LDS of a CU", who);
+    return SMZ_OK;
+}
+// The entry points that only search, and what the `_act` entry points require of their outputs (root_value may be null).
+constexpr ActOut kNoAct = {0.0, nullptr, nullptr, nullptr, nullptr};
+int check_act_outputs(const char *who, const int32_t *action_dev, const double *policy_dev, const double *child_visits_dev) {
+    if (!action_dev || !policy_dev || !child_visits_dev) return fail(SMZ_ERR_INVALID, "%s: null output", who);
+    return SMZ_OK;
+}
+
 // The power table of `temperature` for act_tree (smz_act, and the searches that act in their tail): a new temperature is a
 // synchronous upload (not capturable); the table is reused while the temperature is unchanged.
 int use_pow_table(smz_handle *h, Params &P, double temperature, const double *pow_table_host, smz_stream stream) {

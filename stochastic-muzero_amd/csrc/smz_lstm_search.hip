@@ -10,10 +10,13 @@
 //     k_lstm_recurrent, compiled with the same flags.  The scaled hidden row goes straight into the new node's row of the
 //     handle's hidden array; reward, value and policy go to the tree's slot in LDS for the next round's expansion.
 // Both paths draw the same random words and round alike: the searches are bit-identical (tests/test_gpu_lstm_search.py).
+// The per-lane tree code needs every scalar register a wave has: the kernel's wave-uniform state is pinned or parked in vector
+// registers (in_vgpr / unpark / pin_search_args of smz_search_frame.hpp, which also holds the pb_c staging and the tree's tail).
 // Limits (anything else runs step-wise): one player, 2 or 4 actions, at most 64 trees per wavefront, LDS map <= 160 KB.
 #include "smz_common.hpp"
 #include "smz_handle.hpp"
 #include "smz_lstm_device.hpp"
+#include "smz_search_frame.hpp"
 
 using smz_lstm::kWavesPerWg;
 using smz_mlp::lds_sync;
@@ -21,7 +24,6 @@ using smz_mlp::up4;
 
 namespace {
 
-constexpr int kCus = 256;                    // MI355X
 constexpr int kWgPerCu = 2;                  // workgroups the geometry puts on a CU before a wave takes a second tree
 
 // LDS map (float offsets from the dynamic LDS base): trunk image | pb_c table + reciprocals (doubles) | the descriptor | per wave: one row's
@@ -45,23 +47,6 @@ __host__ __device__ inline LstmLds lstm_lds(const smz_lstm_desc &d, const Params
 
 extern __shared__ float4 smz_lsearch_lds4[];
 
-// A wave-uniform value the per-lane tree code reads, kept in a VECTOR register: the kernel's uniform state (the handle's arrays
-// and geometry, the act outputs, the trunk offsets of the network phase) is more than the 100-odd scalar registers of a wave
-// hold, and the tree phases use these values in per-lane address arithmetic anyway.  The empty asm only names the register class.
-__device__ inline uint32_t in_vgpr(uint32_t v) { asm("" : "+v"(v)); return v; }
-__device__ inline int32_t in_vgpr(int32_t v) { return (int32_t)in_vgpr((uint32_t)v); }
-__device__ inline float in_vgpr(float v) { return __uint_as_float(in_vgpr(__float_as_uint(v))); }
-__device__ inline uint64_t in_vgpr(uint64_t v) { return ((uint64_t)in_vgpr((uint32_t)(v >> 32)) << 32) | in_vgpr((uint32_t)v); }
-__device__ inline int64_t in_vgpr(int64_t v) { return (int64_t)in_vgpr((uint64_t)v); }
-__device__ inline double in_vgpr(double v) { return __longlong_as_double((long long)in_vgpr((uint64_t)__double_as_longlong(v))); }
-// ... and a wave-uniform value of the kernel's own loops (trees per wave, the mask of searched tree slots, the round counter) parked
-// in a vector register while the per-lane tree code runs -- root_init_tree / expand_backup_tree / select_tree need every scalar
-// register a wave has -- and read back where the wave-wide phases start.  (volatile: the read-back is not hoisted out of the
-// rounds, which would keep the scalar copy alive across the tree code again.)
-__device__ inline int fresh(int v) { asm volatile("" : "+v"(v)); return v; }
-__device__ inline int unpark(int v) { asm volatile("" : "+v"(v)); return __builtin_amdgcn_readfirstlane(v); }
-template <class T> __device__ inline T *in_vgpr(T *p) { return reinterpret_cast<T *>(in_vgpr((uint64_t)reinterpret_cast<uintptr_t>(p))); }
-
 // KS: children per expansion as the step-wise kernels compile it (2: the static two-child block code; 0: run-time K)
 template <int MAXA, bool PHX = false, int KS = 0>
 __global__ void __launch_bounds__(kWavesPerWg *kWave, kWgPerCu) k_search_lstm(Params Pin, smz_lstm_desc d, const float *__restrict__ weights,
@@ -76,24 +61,14 @@ __global__ void __launch_bounds__(kWavesPerWg *kWave, kWgPerCu) k_search_lstm(Pa
     if (KS > 0) P.K = KS;
     fix_layout(P, true, KS > 0);
     float *lds = reinterpret_cast<float *>(smz_lsearch_lds4);
-    P.nodes = in_vgpr(P.nodes); P.hdr = in_vgpr(P.hdr); P.path = in_vgpr(P.path); P.mt = in_vgpr(P.mt); P.rng_pos = in_vgpr(P.rng_pos);
-    P.pow_table = in_vgpr(P.pow_table); P.rng_block = in_vgpr(P.rng_block); P.rng_key = in_vgpr(P.rng_key);
-    P.tree_words = in_vgpr(P.tree_words); P.rb_words = in_vgpr(P.rb_words); P.eb_words = in_vgpr(P.eb_words); P.rp_off = in_vgpr(P.rp_off);
-    P.hidden = in_vgpr(P.hidden); P.N = in_vgpr(P.N); P.hs = in_vgpr(P.hs); P.P = in_vgpr(P.P); if (KS == 0) P.K = in_vgpr(P.K);
-    P.disc32 = in_vgpr(P.disc32); P.keep32 = in_vgpr(P.keep32); P.frac = in_vgpr(P.frac); P.alpha = in_vgpr(P.alpha);
-    act.temperature = in_vgpr(act.temperature); act.action = in_vgpr(act.action); act.policy = in_vgpr(act.policy);
-    act.child_visits = in_vgpr(act.child_visits); act.root_value = in_vgpr(act.root_value);
+    pin_search_args(P, act, KS > 0);
     const int lane = threadIdx.x & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const int A = P.A, S = P.S, tpw = P.tpw, sims = P.sims;
     const LstmLds ml = lstm_lds(d, P, tpw);
     P.S = in_vgpr(P.S); P.sims = in_vgpr(P.sims); P.B = in_vgpr(P.B); P.active = in_vgpr(P.active);
     // ---- one-time staging: the seven recurrent trunks, the pb_c table and its reciprocals --------------------------------
     double *pbc_lds = reinterpret_cast<double *>(lds + in_vgpr(ml.pbc));
-    const int n_pbc = sims + 2;
-    for (int i = threadIdx.x; i < n_pbc; i += blockDim.x) {
-        pbc_lds[i] = P.pbc_sqrt[i];
-        pbc_lds[n_pbc + i] = i > 0 ? 1.0 / (double)i : 0.0;      // IEEE division: correctly rounded reciprocals
-    }
+    stage_pbc(pbc_lds, P, sims);
     // the descriptor too: the network phase reads trunk offsets and layer count from LDS into vector registers (in_vgpr's reason:
     // from the kernel arguments, the fourteen trunk pointers of a round would be hoisted into scalar registers for the whole search)
     static_assert(sizeof(smz_lstm_desc) % sizeof(int32_t) == 0, "descriptor is copied word by word");
@@ -198,23 +173,8 @@ __global__ void __launch_bounds__(kWavesPerWg *kWave, kWgPerCu) k_search_lstm(Pa
         P.tpw = ntw;
         packed = wave_stage_rng_from<4, PHX>(P, tree, valid, rng_tile, packed, rng.block());
     }
-    if (valid) {
-        if (sims_v > 0) {
-            rng.load(P.mt + (size_t)tree * kMtN, packed, rng_tile + lane * kRngStride, kRngStage);
-            expand_backup_tree<MAXA, KS>(P, tree, rng, h, outs + lane * slot, outs[lane * slot + A + 1], outs[lane * slot + A],
-                                         path_col(P, tree));
-            packed = rng.pack();
-        }
-        P.hdr[tree] = h;
-        if (act.action) {
-            // the post-search policy / action of game.py:179-232 on the finished tree: the same draws from the same stream
-            // position as a separate smz_act launch
-            act_tree<MAXA>(P, tree, rng, act.temperature, act.action, act.policy, act.child_visits, act.root_value);
-            packed = rng.pack();
-        }
-        P.rng_pos[tree] = packed;
-        rng.save(P, tree);
-    }
+    if (valid)
+        finish_tree<MAXA, KS>(P, tree, rng, h, packed, sims_v, rng_tile + lane * kRngStride, outs + lane * slot, A, path_col(P, tree), act);
 #undef valid
 }
 
@@ -233,13 +193,11 @@ int search_lstm_launch(smz_handle *h, const smz_lstm_desc *desc, const float *we
     DeviceGuard guard(h->cfg.device);
     Params P = h->P;
     // two workgroups per CU before a wave takes a second tree
-    const int waves = kWgPerCu * kCus * kWavesPerWg;
-    const int tpw = (P.B + waves - 1) / waves;
-    if (tpw > kWave) return fail(SMZ_ERR_TOO_LARGE, "smz_search_lstm: more than 64 trees per wavefront: use the step-wise entry points%s");
+    const int tpw = single_launch_tpw(P.B, kWgPerCu * kCus * kWavesPerWg, nullptr);
     P.tpw = tpw;
     const LstmLds ml = lstm_lds(*desc, P, tpw);
+    if (const int rc = check_single_launch_size("smz_search_lstm", tpw, ml.total)) return rc;
     const size_t lds = (size_t)ml.total * sizeof(float);
-    if (lds > 160 * 1024) return fail(SMZ_ERR_TOO_LARGE, "smz_search_lstm: working set exceeds the 160 KB LDS of a CU%s");
     if (act.action && use_pow_table(h, P, act.temperature, pow_table_host, stream) != SMZ_OK) return SMZ_ERR_HIP;
     const int blocks = (P.B + kWavesPerWg * tpw - 1) / (kWavesPerWg * tpw), ks = h->K == 2 ? 2 : 0;
 #define SMZ_LAUNCH_LS(MA, KK) (P.philox ? SMZ_LAUNCH_LS1(MA, true, KK) : SMZ_LAUNCH_LS1(MA, false, KK))
@@ -262,15 +220,14 @@ extern "C" {
 
 int smz_search_lstm(smz_handle *h, const smz_lstm_desc *desc, const float *weights_dev, const float *hidden0_dev,
                     const float *policy0_dev, int train, smz_stream stream) {
-    return search_lstm_launch(h, desc, weights_dev, hidden0_dev, policy0_dev, train, ActOut{0.0, nullptr, nullptr, nullptr, nullptr},
-                              nullptr, stream);
+    return search_lstm_launch(h, desc, weights_dev, hidden0_dev, policy0_dev, train, kNoAct, nullptr, stream);
 }
 
 int smz_search_lstm_act(smz_handle *h, const smz_lstm_desc *desc, const float *weights_dev, const float *hidden0_dev,
                         const float *policy0_dev, int train, double temperature, const double *pow_table_host,
                         int32_t *action_dev, double *policy_dev, double *child_visits_dev, float *root_value_dev,
                         smz_stream stream) {
-    if (!action_dev || !policy_dev || !child_visits_dev) return fail(SMZ_ERR_INVALID, "smz_search_lstm_act: null output%s");
+    if (const int rc = check_act_outputs("smz_search_lstm_act", action_dev, policy_dev, child_visits_dev)) return rc;
     return search_lstm_launch(h, desc, weights_dev, hidden0_dev, policy0_dev, train,
                               ActOut{temperature, action_dev, policy_dev, child_visits_dev, root_value_dev}, pow_table_host, stream);
 }

@@ -26,13 +26,13 @@
 // Limits (anything else runs step-wise): at most 32 actions, at most 64 trees per wavefront, LDS map <= 160 KB, no statistics.
 #include "smz_common.hpp"
 #include "smz_handle.hpp"
+#include "smz_search_frame.hpp"
 
 using smz_mlp::lds_sync;
 using smz_mlp::up4;
 
 namespace {
 
-constexpr int kCus = 256;                    // MI355X
 constexpr int kPlayersWaves = 8;             // wavefronts per workgroup (SMZ_SEARCH_THREADS: 2 per SIMD, 256 VGPRs each)
 static_assert(kPlayersWaves * kWave == SMZ_SEARCH_THREADS, "register-allocated like k_search_mlp");
 
@@ -75,11 +75,7 @@ __global__ void __launch_bounds__(SMZ_SEARCH_THREADS) k_search_mlp_players(Param
     const int A = P.A, S = P.S, tpw = P.tpw;
     const PlayersLds ml = players_lds(d, P, tpw);
     double *pbc_lds = reinterpret_cast<double *>(lds + ml.pbc);
-    const int n_pbc = P.sims + 2;
-    for (int i = threadIdx.x; i < n_pbc; i += blockDim.x) {
-        pbc_lds[i] = P.pbc_sqrt[i];
-        pbc_lds[n_pbc + i] = i > 0 ? 1.0 / (double)i : 0.0;      // IEEE division: correctly rounded reciprocals
-    }
+    stage_pbc(pbc_lds, P, P.sims);
     const int slot = A + 2;
     const int K4in = up4(S + A);
     float *scratch = lds + ml.wave + wave * ml.per_wave;
@@ -178,18 +174,6 @@ __global__ void __launch_bounds__(SMZ_SEARCH_THREADS) k_search_mlp_players(Param
     }
 }
 
-// trees per wavefront: one workgroup of eight wavefronts on each of 256 CUs before a wave takes a second tree.
-// SMZ_PLAYERS_SEARCH_TPW overrides it (tests: a search does not depend on the geometry).
-int players_search_tpw(int B) {
-    const int waves = kCus * kPlayersWaves;
-    int tpw = (B + waves - 1) / waves;
-    if (const char *e = getenv("SMZ_PLAYERS_SEARCH_TPW")) {
-        const int v = atoi(e);
-        if (v >= 1) tpw = v;
-    }
-    return tpw < 1 ? 1 : tpw;
-}
-
 int search_mlp_players_launch(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, int train,
                               ActOut act, const double *pow_table_host, smz_stream stream) {
     if (h && h->large_actions) return refuse_large_actions("smz_search_mlp_players");
@@ -208,11 +192,10 @@ int search_mlp_players_launch(smz_handle *h, const smz_mlp_desc *desc, const flo
     if (const int rc = check_dirichlet_alpha(h, train)) return rc;
     DeviceGuard guard(h->cfg.device);
     Params P = h->P;
-    const int tpw = players_search_tpw(P.B);
-    if (tpw > kWave) return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp_players: more than 64 trees per wavefront: use the step-wise entry points%s");
+    // one workgroup of eight wavefronts on each CU before a wave takes a second tree
+    const int tpw = single_launch_tpw(P.B, kCus * kPlayersWaves, "SMZ_PLAYERS_SEARCH_TPW");
     const PlayersLds ml = players_lds(*desc, P, tpw);
-    if (ml.total * (long long)sizeof(float) > 160 * 1024)
-        return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp_players: working set exceeds the 160 KB LDS of a CU%s");
+    if (const int rc = check_single_launch_size("smz_search_mlp_players", tpw, ml.total)) return rc;
     const size_t lds = (size_t)ml.total * sizeof(float);
     if (act.action && use_pow_table(h, P, act.temperature, pow_table_host, stream) != SMZ_OK) return SMZ_ERR_HIP;
     P.tpw = tpw;
@@ -244,14 +227,13 @@ extern "C" {
 
 int smz_search_mlp_players(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, int train,
                            smz_stream stream) {
-    return search_mlp_players_launch(h, desc, weights_dev, obs_dev, train, ActOut{0.0, nullptr, nullptr, nullptr, nullptr}, nullptr,
-                                     stream);
+    return search_mlp_players_launch(h, desc, weights_dev, obs_dev, train, kNoAct, nullptr, stream);
 }
 
 int smz_search_mlp_players_act(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, int train,
                                double temperature, const double *pow_table_host, int32_t *action_dev, double *policy_dev,
                                double *child_visits_dev, float *root_value_dev, smz_stream stream) {
-    if (!action_dev || !policy_dev || !child_visits_dev) return fail(SMZ_ERR_INVALID, "smz_search_mlp_players_act: null output%s");
+    if (const int rc = check_act_outputs("smz_search_mlp_players_act", action_dev, policy_dev, child_visits_dev)) return rc;
     return search_mlp_players_launch(h, desc, weights_dev, obs_dev, train,
                                      ActOut{temperature, action_dev, policy_dev, child_visits_dev, root_value_dev}, pow_table_host, stream);
 }

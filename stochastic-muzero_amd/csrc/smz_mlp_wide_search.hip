@@ -16,10 +16,13 @@
 // bit for bit (tests/test_gpu_mlp_wide_search.py).
 // Every wavefront of a workgroup reaches every barrier of every round: a wavefront without a searched tree stays in the loop
 // and takes tiles; only a workgroup none of whose trees is searched leaves, as a whole, before the rounds start.
+// The per-lane tree code needs every scalar register a wave has: the kernel's wave-uniform state is pinned or parked in vector
+// registers (in_vgpr / unpark / pin_search_args of smz_search_frame.hpp, which also holds the pb_c staging and the tree's tail).
 // Limits (anything else runs step-wise): one player, 2 or 4 actions, at most 64 trees per wavefront, LDS map <= 160 KB.
 #include "smz_common.hpp"
 #include "smz_handle.hpp"
 #include "smz_mlp_wide_device.hpp"
+#include "smz_search_frame.hpp"
 
 using smz_mlp::kTileLeaves;
 using smz_mlp::kWideOP;
@@ -29,7 +32,6 @@ using smz_mlp::WideDst;
 
 namespace {
 
-constexpr int kCus = 256;                    // MI355X
 constexpr int kWgPerCu = 1;                  // workgroups the geometry puts on a CU before a wave takes a second tree (register-bound: see DESIGN.md 3.6)
 constexpr int kSearchWaves = 4;              // wavefronts per workgroup
 
@@ -55,19 +57,6 @@ __host__ __device__ inline WideLds wide_lds(int A, int sims, int tpw) {
 
 extern __shared__ float4 smz_wsearch_lds4[];
 
-// A wave-uniform value the per-lane tree code reads, kept in a VECTOR register, and a wave-uniform value of the kernel's own loops
-// parked in one while the per-lane tree code runs: the devices of smz_lstm_search.hip, for its reason (root_init_tree /
-// expand_backup_tree / select_tree need every scalar register a wave has).  The empty asm only names the register class.
-__device__ inline uint32_t in_vgpr(uint32_t v) { asm("" : "+v"(v)); return v; }
-__device__ inline int32_t in_vgpr(int32_t v) { return (int32_t)in_vgpr((uint32_t)v); }
-__device__ inline float in_vgpr(float v) { return __uint_as_float(in_vgpr(__float_as_uint(v))); }
-__device__ inline uint64_t in_vgpr(uint64_t v) { return ((uint64_t)in_vgpr((uint32_t)(v >> 32)) << 32) | in_vgpr((uint32_t)v); }
-__device__ inline int64_t in_vgpr(int64_t v) { return (int64_t)in_vgpr((uint64_t)v); }
-__device__ inline double in_vgpr(double v) { return __longlong_as_double((long long)in_vgpr((uint64_t)__double_as_longlong(v))); }
-__device__ inline int fresh(int v) { asm volatile("" : "+v"(v)); return v; }
-__device__ inline int unpark(int v) { asm volatile("" : "+v"(v)); return __builtin_amdgcn_readfirstlane(v); }
-template <class T> __device__ inline T *in_vgpr(T *p) { return reinterpret_cast<T *>(in_vgpr((uint64_t)reinterpret_cast<uintptr_t>(p))); }
-
 // KS: children per expansion as the step-wise kernels compile it (2: the static two-child block code; 0: run-time K)
 template <int MAXA, bool PHX = false, int KS = 0>
 __global__ void __launch_bounds__(kSearchWaves *kWave, kWgPerCu) k_search_mlp_wide(Params Pin, smz_mlp_desc d, const float *__restrict__ weights,
@@ -82,13 +71,7 @@ __global__ void __launch_bounds__(kSearchWaves *kWave, kWgPerCu) k_search_mlp_wi
     if (KS > 0) P.K = KS;
     fix_layout(P, true, KS > 0);
     float *lds = reinterpret_cast<float *>(smz_wsearch_lds4);
-    P.nodes = in_vgpr(P.nodes); P.hdr = in_vgpr(P.hdr); P.path = in_vgpr(P.path); P.mt = in_vgpr(P.mt); P.rng_pos = in_vgpr(P.rng_pos);
-    P.pow_table = in_vgpr(P.pow_table); P.rng_block = in_vgpr(P.rng_block); P.rng_key = in_vgpr(P.rng_key);
-    P.tree_words = in_vgpr(P.tree_words); P.rb_words = in_vgpr(P.rb_words); P.eb_words = in_vgpr(P.eb_words); P.rp_off = in_vgpr(P.rp_off);
-    P.hidden = in_vgpr(P.hidden); P.N = in_vgpr(P.N); P.hs = in_vgpr(P.hs); P.P = in_vgpr(P.P); if (KS == 0) P.K = in_vgpr(P.K);
-    P.disc32 = in_vgpr(P.disc32); P.keep32 = in_vgpr(P.keep32); P.frac = in_vgpr(P.frac); P.alpha = in_vgpr(P.alpha);
-    act.temperature = in_vgpr(act.temperature); act.action = in_vgpr(act.action); act.policy = in_vgpr(act.policy);
-    act.child_visits = in_vgpr(act.child_visits); act.root_value = in_vgpr(act.root_value);
+    pin_search_args(P, act, KS > 0);
     const int lane = threadIdx.x & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const int A = P.A, S = P.S, tpw = P.tpw, sims = P.sims;
     const WideLds ml = wide_lds(A, sims, tpw);
@@ -118,11 +101,7 @@ __global__ void __launch_bounds__(kSearchWaves *kWave, kWgPerCu) k_search_mlp_wi
     const int first_v = in_vgpr(vmask != 0ull ? (int)__builtin_ctzll(vmask) : 0);
 
     // ---- one-time staging: the pb_c table and its reciprocals; does the workgroup search anything? -------------------------
-    const int n_pbc = sims + 2;
-    for (int i = threadIdx.x; i < n_pbc; i += blockDim.x) {
-        pbc_lds[i] = P.pbc_sqrt[i];
-        pbc_lds[n_pbc + i] = i > 0 ? 1.0 / (double)i : 0.0;      // IEEE division: correctly rounded reciprocals
-    }
+    stage_pbc(pbc_lds, P, sims);
     if (lane == 0) flags[wave] = vmask != 0ull ? 1 : 0;
     __syncthreads();
     // every tree of the workgroup switched off (smz_set_active): all four wavefronts leave here, before the rounds' barriers
@@ -229,35 +208,9 @@ __global__ void __launch_bounds__(kSearchWaves *kWave, kWgPerCu) k_search_mlp_wi
             packed = wave_stage_rng_from<4, PHX>(P, tree, valid, rng_tile, packed, rng.block());
         }
     }
-    if (valid) {
-        if (sims_v > 0) {
-            rng.load(P.mt + (size_t)tree * kMtN, packed, rng_tile + lane * kRngStride, kRngStage);
-            expand_backup_tree<MAXA, KS>(P, tree, rng, h, outs, outs[A + 1], outs[A], path_col(P, tree));
-            packed = rng.pack();
-        }
-        P.hdr[tree] = h;
-        if (act.action) {
-            // the post-search policy / action of game.py:179-232 on the finished tree: the same draws from the same stream
-            // position as a separate smz_act launch
-            act_tree<MAXA>(P, tree, rng, act.temperature, act.action, act.policy, act.child_visits, act.root_value);
-            packed = rng.pack();
-        }
-        P.rng_pos[tree] = packed;
-        rng.save(P, tree);
-    }
+    if (valid)
+        finish_tree<MAXA, KS>(P, tree, rng, h, packed, sims_v, rng_tile + lane * kRngStride, outs, A, path_col(P, tree), act);
 #undef valid
-}
-
-// trees per wavefront: kWgPerCu workgroups of four wavefronts on each of 256 CUs before a wave takes a second tree.
-// SMZ_WIDE_SEARCH_TPW overrides it (tests: a search does not depend on the geometry).
-int wide_search_tpw(int B) {
-    const int waves = kWgPerCu * kCus * kSearchWaves;
-    int tpw = (B + waves - 1) / waves;
-    if (const char *e = getenv("SMZ_WIDE_SEARCH_TPW")) {
-        const int v = atoi(e);
-        if (v >= 1) tpw = v;
-    }
-    return tpw < 1 ? 1 : tpw;
 }
 
 int search_mlp_wide_launch(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *hidden0_dev,
@@ -277,11 +230,11 @@ int search_mlp_wide_launch(smz_handle *h, const smz_mlp_desc *desc, const float 
     if (const int rc = check_dirichlet_alpha(h, train)) return rc;
     DeviceGuard guard(h->cfg.device);
     Params P = h->P;
-    const int tpw = wide_search_tpw(P.B);
-    if (tpw > kWave) return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp_wide: more than 64 trees per wavefront: use the step-wise entry points%s");
+    // kWgPerCu workgroups of four wavefronts on each CU before a wave takes a second tree
+    const int tpw = single_launch_tpw(P.B, kWgPerCu * kCus * kSearchWaves, "SMZ_WIDE_SEARCH_TPW");
     const WideLds ml = wide_lds(P.A, P.sims, tpw);
+    if (const int rc = check_single_launch_size("smz_search_mlp_wide", tpw, ml.total)) return rc;
     const size_t lds = (size_t)ml.total * sizeof(float);
-    if (lds > 160 * 1024) return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp_wide: working set exceeds the 160 KB LDS of a CU%s");
     if (act.action && use_pow_table(h, P, act.temperature, pow_table_host, stream) != SMZ_OK) return SMZ_ERR_HIP;
     P.tpw = tpw;
     const int blocks = (P.B + kSearchWaves * tpw - 1) / (kSearchWaves * tpw), ks = h->K == 2 ? 2 : 0;
@@ -305,15 +258,14 @@ extern "C" {
 
 int smz_search_mlp_wide(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *hidden0_dev,
                         const float *policy0_dev, int train, smz_stream stream) {
-    return search_mlp_wide_launch(h, desc, weights_dev, hidden0_dev, policy0_dev, train,
-                                  ActOut{0.0, nullptr, nullptr, nullptr, nullptr}, nullptr, stream);
+    return search_mlp_wide_launch(h, desc, weights_dev, hidden0_dev, policy0_dev, train, kNoAct, nullptr, stream);
 }
 
 int smz_search_mlp_wide_act(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *hidden0_dev,
                             const float *policy0_dev, int train, double temperature, const double *pow_table_host,
                             int32_t *action_dev, double *policy_dev, double *child_visits_dev, float *root_value_dev,
                             smz_stream stream) {
-    if (!action_dev || !policy_dev || !child_visits_dev) return fail(SMZ_ERR_INVALID, "smz_search_mlp_wide_act: null output%s");
+    if (const int rc = check_act_outputs("smz_search_mlp_wide_act", action_dev, policy_dev, child_visits_dev)) return rc;
     return search_mlp_wide_launch(h, desc, weights_dev, hidden0_dev, policy0_dev, train,
                                   ActOut{temperature, action_dev, policy_dev, child_visits_dev, root_value_dev}, pow_table_host, stream);
 }

@@ -83,7 +83,7 @@ int smz_search_mlp_act(smz_handle *h, const smz_mlp_desc *desc, const float *wei
                        double temperature, const double *pow_table_host, int32_t *action_dev, double *policy_dev,
                        double *child_visits_dev, float *root_value_dev, smz_stream stream) {
     if (h && h->large_actions) return refuse_large_actions("smz_search_mlp_act");
-    if (!action_dev || !policy_dev || !child_visits_dev) return fail(SMZ_ERR_INVALID, "smz_search_mlp_act: null output%s");
+    if (const int rc = check_act_outputs("smz_search_mlp_act", action_dev, policy_dev, child_visits_dev)) return rc;
     if (h && h->P.n_cycle > 1) return refuse_multi_player("smz_search_mlp_act");
     return smz_internal_search_launch_narrow(h, desc, weights_dev, obs_dev, train,
                                              SearchActArgs{temperature, action_dev, policy_dev, child_visits_dev, root_value_dev,

@@ -756,8 +756,9 @@ struct SearchLaunch {
         if (const char *e = getenv("SMZ_SEARCH_TPW")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) tpw = v; }
         P.tpw = tpw;
         const MegaLds ml = mega_lds(*desc, P, tpw, false, kWaves);
-        lds = ((size_t)ml.wave_off + (size_t)kWaves * ml.per_wave) * sizeof(float);
-        if (lds > 160 * 1024) return fail(SMZ_ERR_TOO_LARGE, "smz_search_mlp: working set exceeds the 160 KB LDS of a CU%s");
+        const long long lds_floats = (long long)ml.wave_off + (long long)kWaves * ml.per_wave;
+        if (const int rc = check_single_launch_size("smz_search_mlp", tpw, lds_floats)) return rc;
+        lds = (size_t)lds_floats * sizeof(float);
         if (a.action && use_pow_table(h, P, a.temperature, pow_table_host, stream) != SMZ_OK) return SMZ_ERR_HIP;
         blocks = (P.B + kWaves * tpw - 1) / (kWaves * tpw);
         threads = kWaves * kWave;

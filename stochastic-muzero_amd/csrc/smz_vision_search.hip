@@ -647,8 +647,8 @@ int search_vision_launch(smz_handle *h, const smz_vision_desc *desc, const float
     Params P = h->P;
     P.tpw = 1;
     const VisLds ml = vis_lds(P, P.A);
+    if (const int rc = check_single_launch_size("smz_search_vision", P.tpw, ml.total)) return rc;
     const size_t lds = (size_t)ml.total * sizeof(float);
-    if (lds > 160 * 1024) return fail(SMZ_ERR_TOO_LARGE, "smz_search_vision: working set exceeds the 160 KB LDS of a CU%s");
     if (act.action && use_pow_table(h, P, act.temperature, pow_table_host, stream) != SMZ_OK) return SMZ_ERR_HIP;
     const int blocks = (P.B + kVW - 1) / kVW;
     const bool eq = P.A == h->maxa;                  // (A <= 4: the bucket is 2 or 4)
@@ -673,15 +673,14 @@ extern "C" {
 
 int smz_search_vision(smz_handle *h, const smz_vision_desc *desc, const float *weights_dev, const float *hidden0_dev,
                       const float *policy0_dev, int train, smz_stream stream) {
-    return search_vision_launch(h, desc, weights_dev, hidden0_dev, policy0_dev, train, ActOut{0.0, nullptr, nullptr, nullptr, nullptr},
-                                nullptr, stream);
+    return search_vision_launch(h, desc, weights_dev, hidden0_dev, policy0_dev, train, kNoAct, nullptr, stream);
 }
 
 int smz_search_vision_act(smz_handle *h, const smz_vision_desc *desc, const float *weights_dev, const float *hidden0_dev,
                           const float *policy0_dev, int train, double temperature, const double *pow_table_host,
                           int32_t *action_dev, double *policy_dev, double *child_visits_dev, float *root_value_dev,
                           smz_stream stream) {
-    if (!action_dev || !policy_dev || !child_visits_dev) return fail(SMZ_ERR_INVALID, "smz_search_vision_act: null output%s");
+    if (const int rc = check_act_outputs("smz_search_vision_act", action_dev, policy_dev, child_visits_dev)) return rc;
     return search_vision_launch(h, desc, weights_dev, hidden0_dev, policy0_dev, train,
                                 ActOut{temperature, action_dev, policy_dev, child_visits_dev, root_value_dev}, pow_table_host, stream);
 }

@@ -77,7 +77,7 @@ def test_lstm_search_kernels_use_no_scratch_and_spill_nothing(tmp_path):
     spills.
 
     The per-lane tree code (root_init_tree's Dirichlet draws above all) takes every scalar register of a wave, so the kernel keeps
-    its own wave-uniform state in vector registers (in_vgpr / unpark, smz_lstm_search.hip) and runs the root expansion without a
+    its own wave-uniform state in vector registers (in_vgpr / unpark, smz_search_frame.hpp) and runs the root expansion without a
     branch.  With that: 212-234 vector registers of the 256 a wave may hold at two workgroups per CU, nothing
     spilled (82-126 scalar registers were, before)."""
     out = tmp_path / "lstm_search.s"

@@ -78,8 +78,8 @@ def test_wide_search_kernels_use_no_scratch_and_spill_no_vector_registers(tmp_pa
     at the one workgroup per CU the kernel is built for (__launch_bounds__(256, 1): a wave may hold 512 vector registers).
 
     Reported, not asserted (DESIGN.md 3.6 has the figures of this build): the spilled scalar registers -- the per-lane tree code
-    takes every scalar register of a wave, and the descriptor offsets of the network phase are kept across it in lanes of
-    vector registers -- and the vector / accumulator register counts.  LDS is dynamic (sized on the host: wide_lds)."""
+    takes every scalar register of a wave (in_vgpr / unpark, smz_search_frame.hpp), and the descriptor offsets of the network
+    phase are kept across it in lanes of vector registers -- and the vector / accumulator register counts.  LDS is dynamic (sized on the host: wide_lds)."""
     out = tmp_path / "mlp_wide_search.s"
     r = subprocess.run([HIPCC, *FLAGS, "-o", str(out), "smz_mlp_wide_search.hip"], cwd=CSRC, capture_output=True, text=True,
                        timeout=900)

@@ -9,10 +9,14 @@ to its .Lfunc_end -- instructions and the .amdhsa_kernel block with the register
 after normalisation: __hip_cuid_ lines (they depend on the file name) are dropped, the per-function index is stripped from
 .LBB<n>_<m>, .Lfunc_begin<n>, .Lfunc_end<n>, jump-table labels and the loop comments (the assembler numbers functions by
 their position in the unit), the unit-wide counter from .Lpost_getpc<n> (long branches), and runs of blanks count as one.
-Kernels present on one side only are listed.  Exit status 1 if a common kernel differs or a file is missing.
+Kernels present on one side only are listed.  For a kernel that differs, one line says how far apart the two sides are --
+whether the .amdhsa_kernel block is identical, the number of instruction lines on each side, and the size of the symmetric
+difference of the two sides as multisets of normalised lines (0: a reordering only; 2: one line changed) -- before the first
+40 lines of the diff.  Exit status 1 if a common kernel differs or a file is missing.
 """
 import difflib
 import os
+from collections import Counter
 import re
 import sys
 
@@ -39,6 +43,33 @@ def kernels(path):
     return out
 
 
+def resource_block(lines):
+    """the lines from .amdhsa_kernel to .end_amdhsa_kernel: registers, scratch, LDS and the other launch figures"""
+    start = next((i for i, l in enumerate(lines) if _KERNEL.match(l)), len(lines))
+    end = next((i for i in range(start, len(lines)) if lines[i].strip() == ".end_amdhsa_kernel"), len(lines) - 1)
+    return lines[start:end + 1]
+
+
+def instruction_lines(lines):
+    """what is neither blank, a label, a directive nor a comment, without its trailing comment"""
+    out = []
+    for l in lines:
+        l = l.split(";")[0].strip()
+        if l and not l.startswith(".") and not l.endswith(":"):
+            out.append(l)
+    return out
+
+
+def difference_summary(a, b):
+    """How far apart two differing kernels are.  The multiset difference counts lines without regard to their order: a
+    reordering alone gives 0, one changed line (say, the operands of a commutative instruction swapped) gives 2."""
+    same = "identical" if resource_block(a) == resource_block(b) else "DIFFERENT"
+    ca, cb = Counter(a), Counter(b)
+    moved = sum(((ca - cb) + (cb - ca)).values())
+    return (f".amdhsa_kernel block {same}; instructions {len(instruction_lines(a))} | {len(instruction_lines(b))}; "
+            f"multiset difference {moved} lines")
+
+
 def main(argv):
     if len(argv) != 3:
         print(__doc__)
@@ -61,6 +92,7 @@ def main(argv):
         for k in differ:
             bad = True
             print(f"  DIFFERS: {k}")
+            print("    " + difference_summary(a[k], b[k]))
             for l in list(difflib.unified_diff(a[k], b[k], "a", "b", n=1, lineterm=""))[:40]:
                 print("    " + l)
     return 1 if bad else 0

@@ -491,6 +491,33 @@ int smz_mlp_recurrent_wide(const smz_mlp_desc *desc, const float *weights_dev, c
                            const uint8_t *branch_dev, float *hidden_out_dev, float *reward_out_dev, float *policy_out_dev,
                            float *value_out_dev, int B, smz_stream stream);
 
+/* The recurrent mlp_model networks for up to SMZ_MAX_ACTIONS_LARGE actions: H <= 128, 2 S <= 128, 1 <= A <= 1024, no limit on
+ * A + S (SMZ_ERR_TOO_LARGE beyond those; SMZ_ERR_INVALID for a null descriptor or a non-positive dimension).
+ * smz_mlp_layout_large fills the same descriptor (OP = 128) for a packed image that differs from smz_mlp_layout_wide's in the
+ * two layers whose width grows with the action count; R8(x) = x rounded up to a multiple of 8, "wide matrix" = K rows padded
+ * to R8(K), element (k, o) at base + ((k / 4) * 128 + o) * 4 + k % 4, padding zero:
+ *   off[0] dyn_in, off[1] ady_in   the hidden part, a wide matrix of the S hidden-state rows of the torch weight (R8(S) x 128
+ *                                  floats), then the action table [A][128]: element (a, o) at off + R8(S) * 128 + a * 128 + o
+ *                                  = weight of input S + a for neuron o.  Linear(S + A, H) on [hidden | onehot(a)] is
+ *                                  bias + hidden . W[:S] + table[a]: the kernel takes the action, never a one-hot row
+ *   off[10] pre_out, off[11] apr_out   P + 1 panels, P = ceil(A / 128), each a wide matrix of H rows (R8(H) x 128 floats):
+ *                                  panel p < P holds policy columns 128 p .. min(A, 128 p + 128) - 1, panel P the S value columns
+ *   off[15 + 10], off[15 + 11]     P + 1 bias vectors of 128 floats, one per panel
+ *   every other matrix and bias    as smz_mlp_layout_wide lays it out (the representation matrices are present and unused)
+ * total_floats = 128 * (2 (R8(S) + A) + 4 M + 3 R8(H) + 2 R8(S) + 2 (P + 1) R8(H) + R8(obs) + M + 13 + 2 (P + 1)), M = R8(H) if
+ * number_of_hidden_layer > 0 else 0.
+ * smz_mlp_recurrent_large: one launch, for every row the pair of networks its branch flag names (non-zero: dynamics +
+ * prediction; zero: afterstate dynamics + afterstate prediction, reward 0) on parent_hidden_dev [B,S], last_action_dev [B] and
+ * branch_dev [B] as smz_select writes them -> the outputs of smz_mlp_recurrent_wide.  A last_action outside [0, A) (the row of
+ * a tree that is switched off: smz_select leaves it unwritten) is evaluated as action 0.  16-leaf tiles on the matrix cores,
+ * weights streamed from L2, the softmax carried across the panels; no allocation, no host read: safe under stream capture.
+ * SMZ_ERR_INVALID: a null pointer, B < 1, a descriptor smz_mlp_layout_large would not produce.
+ * neural_network_mlp_model.py:5-250, muzero_model.py:844-909. */
+int smz_mlp_layout_large(smz_mlp_desc *desc);
+int smz_mlp_recurrent_large(const smz_mlp_desc *desc, const float *weights_dev, const float *parent_hidden_dev,
+                            const int32_t *last_action_dev, const uint8_t *branch_dev, float *hidden_out_dev,
+                            float *reward_out_dev, float *policy_out_dev, float *value_out_dev, int B, smz_stream stream);
+
 /* ---- synthetic environment + trajectory record (self_play.py:63-98 loop body around the search) -------------- */
 /* CartPole-v1 shaped Euler step on device (float64 state, float32 observation), used for the synthetic
  * fixed-length episodes of the benchmark: state_dev [B,4] f64 in/out, action_dev [B] i32,

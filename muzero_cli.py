@@ -62,6 +62,15 @@ def mcts_kwargs(config, num_simulations=None):
     return kw
 
 
+def set_heads_backend(model, config):
+    """"large_action_heads": true in the monte_carlo_tree_search section (not a key of the reference's configs, and not an
+    argument of BatchedMCTS: mcts_kwargs leaves it out) makes model.heads(device) hand out the large-action HIP heads
+    (Muzero.heads_backend = "large"); a config without the key leaves the model alone."""
+    if config["monte_carlo_tree_search"].get("large_action_heads"):
+        model.heads_backend = "large"
+    return model
+
+
 def make_env(name, num_envs, device, seed, limit=0, on_end="continue"):
     """The vectorised environment of a run: the built-in device-resident CartPole, or -- for any other name -- gymnasium
     environments stepped on the host behind the pinned-memory adapter (envs.HostVecEnv; needs gymnasium installed)."""
@@ -114,7 +123,7 @@ def main(argv):
     if modes["play"] or modes["benchmark"]:
         p = config["play_game_from_checkpoint"]
         n_env = opts["envs"] or (100 if modes["benchmark"] else 1)
-        model = model_mod.Muzero.from_checkpoint(opts["checkpoint_dir"], tag=p["model_tag"])
+        model = set_heads_backend(model_mod.Muzero.from_checkpoint(opts["checkpoint_dir"], tag=p["model_tag"]), config)
         sims = config["monte_carlo_tree_search"]["maxium_action_sample"] if opts["reference_play_sims"] else None
         search = mcts_mod.BatchedMCTS(n_env, **mcts_kwargs(config, sims))
         search.seed(np.arange(n_env, dtype=np.uint64) + np.uint64(config["random_seed"]["np_random_seed"]))
@@ -143,6 +152,7 @@ def main(argv):
         else:
             probe = make_env(config["game"]["env"], 1, device, 0)
             model = fresh_model(mz, probe.obs_dim, probe.num_actions, lc["model_tag_number"])
+        set_heads_backend(model, config)
         search = mcts_mod.BatchedMCTS(n_env, **mcts_kwargs(config))
         search.seed(np.arange(n_env, dtype=np.uint64) + np.uint64(config["random_seed"]["np_random_seed"]))
         limit = int(config["gameplay"]["limit_of_game_play"])

@@ -10,6 +10,8 @@
 // tiles with the weights streamed from L2 -- A operands as 8-byte global loads of a 128-wide packed image
 // (smz_mlp_layout_wide), prefetched one input group ahead of the MFMAs that consume them; layers are 8 tiles of 16
 // neurons, dimensions are run-time values.
+// The large-action head kernels (smz_mlp_large.hip: any A up to 1024) take the same pieces -- wide_layer, wide_nets,
+// wide_trunk_store, wide_between -- and replace only the two layers whose width depends on the action count.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -80,53 +82,52 @@ struct WideDst {
     float *hidden, *policy, *value, *reward;
 };
 
-// ONE tile of up to 16 leaves of one branch (ady: the afterstate pair of networks), by one wavefront.
-//   tile     the wavefront's kWideTileFloats of LDS
-//   count    leaves in the tile (>= 1; may exceed 16: the tile then takes the first 16)
-//   in       in(lf, k): input k < S + A of leaf lf < min(count, 16) -- [hidden row | one-hot action]
-//   dst      dst(lf): the destinations of leaf lf < min(count, 16)
-// A ragged tile repeats its first leaf in the unused columns; nothing is stored for them.
-template <class In, class Dst>
-__device__ inline void wide_tile(const smz_mlp_desc &d, const float *__restrict__ weights, float *tile, int count, bool ady, int lane,
-                                 In in, Dst dst) {
-    const int S = d.S, A = d.A, H = d.H, half = S / 2, XW = S + A;
-    const int K8x = (XW + 7) >> 3, K8h = (H + 7) >> 3, K8s = (S + 7) >> 3;
+// the matrices and biases of one branch's pair of networks (ady: afterstate dynamics + afterstate prediction)
+// (selects between constant-index descriptor entries: a run-time index would put the table in scratch)
+struct WideNets {
+    int w_in, b_in, w_mid, b_mid, w_out, b_out, wp_in, bp_in, wp_mid, bp_mid, wp_out, bp_out;
+};
+__device__ inline WideNets wide_nets(const smz_mlp_desc &d, bool ady) {
+    WideNets n;
+    n.w_in = ady ? d.off[M_ADY_IN] : d.off[M_DYN_IN]; n.b_in = ady ? d.off[M_COUNT + M_ADY_IN] : d.off[M_COUNT + M_DYN_IN];
+    n.w_out = ady ? d.off[M_ADY_OUT] : d.off[M_DYN_OUT]; n.b_out = ady ? d.off[M_COUNT + M_ADY_OUT] : d.off[M_COUNT + M_DYN_OUT];
+    n.wp_in = ady ? d.off[M_APR_IN] : d.off[M_PRE_IN]; n.bp_in = ady ? d.off[M_COUNT + M_APR_IN] : d.off[M_COUNT + M_PRE_IN];
+    n.wp_out = ady ? d.off[M_APR_OUT] : d.off[M_PRE_OUT]; n.bp_out = ady ? d.off[M_COUNT + M_APR_OUT] : d.off[M_COUNT + M_PRE_OUT];
+    n.w_mid = ady ? d.off[M_ADY_MID] : d.off[M_DYN_MID]; n.b_mid = ady ? d.off[M_COUNT + M_ADY_MID] : d.off[M_COUNT + M_DYN_MID];
+    n.wp_mid = ady ? d.off[M_APR_MID] : d.off[M_PRE_MID]; n.bp_mid = ady ? d.off[M_COUNT + M_APR_MID] : d.off[M_COUNT + M_PRE_MID];
+    return n;
+}
+
+// ELU of a trunk layer's outputs into the tile (neuron n = input n of the next layer)
+__device__ inline void wide_trunk_store(float *tile, const v4f (&y)[kWideTiles], int lane) {
     const int g = lane >> 4, j = lane & 15;
-    const bool mine = j < count;
-    const WideDst out = dst(mine ? j : 0);
-    // network inputs [hidden | one-hot] -> tile, zero beyond them up to the layer's 8-input groups
-    for (int i = lane; i < kTileLeaves * 8 * K8x; i += kWave) {
-        const int lf = i / (8 * K8x), k = i % (8 * K8x);
-        tile[((k >> 1) * kTileLeaves + lf) * 2 + (k & 1)] = k < XW ? in(lf < count ? lf : 0, k) : 0.f;
-    }
-    lds_sync();
-    // (selects between constant-index descriptor entries: a run-time index would put the table in scratch)
-    const int w_in = ady ? d.off[M_ADY_IN] : d.off[M_DYN_IN], b_in = ady ? d.off[M_COUNT + M_ADY_IN] : d.off[M_COUNT + M_DYN_IN];
-    const int w_out = ady ? d.off[M_ADY_OUT] : d.off[M_DYN_OUT], b_out = ady ? d.off[M_COUNT + M_ADY_OUT] : d.off[M_COUNT + M_DYN_OUT];
-    const int wp_in = ady ? d.off[M_APR_IN] : d.off[M_PRE_IN], bp_in = ady ? d.off[M_COUNT + M_APR_IN] : d.off[M_COUNT + M_PRE_IN];
-    const int wp_out = ady ? d.off[M_APR_OUT] : d.off[M_PRE_OUT], bp_out = ady ? d.off[M_COUNT + M_APR_OUT] : d.off[M_COUNT + M_PRE_OUT];
-    const int w_mid = ady ? d.off[M_ADY_MID] : d.off[M_DYN_MID], b_mid = ady ? d.off[M_COUNT + M_ADY_MID] : d.off[M_COUNT + M_DYN_MID];
-    const int wp_mid = ady ? d.off[M_APR_MID] : d.off[M_PRE_MID], bp_mid = ady ? d.off[M_COUNT + M_APR_MID] : d.off[M_COUNT + M_PRE_MID];
-    v4f y[kWideTiles];
-    auto trunk_store = [&]() {
 #pragma unroll
-        for (int t = 0; t < kWideTiles; t++) {
-            const int nn = 16 * t + 4 * g;
-            *reinterpret_cast<float2 *>(tile + (((nn >> 1) + 0) * kTileLeaves + j) * 2) = make_float2(elu(y[t][0]), elu(y[t][1]));
-            *reinterpret_cast<float2 *>(tile + (((nn >> 1) + 1) * kTileLeaves + j) * 2) = make_float2(elu(y[t][2]), elu(y[t][3]));
-        }
-    };
-    wide_layer(weights + w_in, weights + b_in, tile, K8x, lane, y);
+    for (int t = 0; t < kWideTiles; t++) {
+        const int nn = 16 * t + 4 * g;
+        *reinterpret_cast<float2 *>(tile + (((nn >> 1) + 0) * kTileLeaves + j) * 2) = make_float2(elu(y[t][0]), elu(y[t][1]));
+        *reinterpret_cast<float2 *>(tile + (((nn >> 1) + 1) * kTileLeaves + j) * 2) = make_float2(elu(y[t][2]), elu(y[t][3]));
+    }
+}
+
+// Everything between the two layers whose width depends on the action count.  In: y = the sums of the dynamics input layer
+// (its inputs in the tile are dead).  The dynamics trunk, its output layer, scale_to_bound_action and the reward decode, the
+// prediction input layer and trunk.  Out: the prediction trunk in the tile (the inputs of the prediction output layer), the
+// scaled hidden row stored to `hidden` (mine: this lane's leaf exists), the decoded reward returned (0 on the afterstate branch).
+__device__ inline float wide_between(const smz_mlp_desc &d, const float *__restrict__ weights, const WideNets &n, float *tile, bool ady,
+                                     int lane, bool mine, float *hidden, v4f (&y)[kWideTiles]) {
+    const int S = d.S, H = d.H, half = S / 2;
+    const int K8h = (H + 7) >> 3, K8s = (S + 7) >> 3;
+    const int g = lane >> 4, j = lane & 15;
     lds_sync();
-    trunk_store();
+    wide_trunk_store(tile, y, lane);
     lds_sync();
     for (int l = 0; l < d.L; l++) {          // the SAME Linear(H, H) + ELU applied L times (neural_network_mlp_model.py:122-142)
-        wide_layer(weights + w_mid, weights + b_mid, tile, K8h, lane, y);
+        wide_layer(weights + n.w_mid, weights + n.b_mid, tile, K8h, lane, y);
         lds_sync();
-        trunk_store();
+        wide_trunk_store(tile, y, lane);
         lds_sync();
     }
-    wide_layer(weights + w_out, weights + b_out, tile, K8h, lane, y);
+    wide_layer(weights + n.w_out, weights + n.b_out, tile, K8h, lane, y);
     float reward = 0.f;
     {   // dynamics: [reward logits 0..S-1 | next state S..2S-1]; afterstate dynamics: next state 0..S-1
         const int lo = ady ? 0 : S;
@@ -163,7 +164,7 @@ __device__ inline void wide_tile(const smz_mlp_desc &d, const float *__restrict_
                 if (k >= 0 && k < S) {
                     const float hv = __fdividef(y[t][r] - mn, sc);
                     tile[((k >> 1) * kTileLeaves + j) * 2 + (k & 1)] = hv;
-                    if (mine) out.hidden[k] = hv;
+                    if (mine) hidden[k] = hv;
                 }
             }
         for (int i = lane; i < kTileLeaves * (8 * K8s - S); i += kWave) {          // zero inputs S .. 8 K8s - 1
@@ -172,17 +173,44 @@ __device__ inline void wide_tile(const smz_mlp_desc &d, const float *__restrict_
         }
     }
     lds_sync();
-    wide_layer(weights + wp_in, weights + bp_in, tile, K8s, lane, y);
+    wide_layer(weights + n.wp_in, weights + n.bp_in, tile, K8s, lane, y);
     lds_sync();
-    trunk_store();
+    wide_trunk_store(tile, y, lane);
     lds_sync();
     for (int l = 0; l < d.L; l++) {
-        wide_layer(weights + wp_mid, weights + bp_mid, tile, K8h, lane, y);
+        wide_layer(weights + n.wp_mid, weights + n.bp_mid, tile, K8h, lane, y);
         lds_sync();
-        trunk_store();
+        wide_trunk_store(tile, y, lane);
         lds_sync();
     }
-    wide_layer(weights + wp_out, weights + bp_out, tile, K8h, lane, y);
+    return reward;
+}
+
+// ONE tile of up to 16 leaves of one branch (ady: the afterstate pair of networks), by one wavefront.
+//   tile     the wavefront's kWideTileFloats of LDS
+//   count    leaves in the tile (>= 1; may exceed 16: the tile then takes the first 16)
+//   in       in(lf, k): input k < S + A of leaf lf < min(count, 16) -- [hidden row | one-hot action]
+//   dst      dst(lf): the destinations of leaf lf < min(count, 16)
+// A ragged tile repeats its first leaf in the unused columns; nothing is stored for them.
+template <class In, class Dst>
+__device__ inline void wide_tile(const smz_mlp_desc &d, const float *__restrict__ weights, float *tile, int count, bool ady, int lane,
+                                 In in, Dst dst) {
+    const int S = d.S, A = d.A, H = d.H, half = S / 2, XW = S + A;
+    const int K8x = (XW + 7) >> 3, K8h = (H + 7) >> 3;
+    const int g = lane >> 4, j = lane & 15;
+    const bool mine = j < count;
+    const WideDst out = dst(mine ? j : 0);
+    // network inputs [hidden | one-hot] -> tile, zero beyond them up to the layer's 8-input groups
+    for (int i = lane; i < kTileLeaves * 8 * K8x; i += kWave) {
+        const int lf = i / (8 * K8x), k = i % (8 * K8x);
+        tile[((k >> 1) * kTileLeaves + lf) * 2 + (k & 1)] = k < XW ? in(lf < count ? lf : 0, k) : 0.f;
+    }
+    lds_sync();
+    const WideNets n = wide_nets(d, ady);
+    v4f y[kWideTiles];
+    wide_layer(weights + n.w_in, weights + n.b_in, tile, K8x, lane, y);
+    const float reward = wide_between(d, weights, n, tile, ady, lane, mine, out.hidden, y);
+    wide_layer(weights + n.wp_out, weights + n.bp_out, tile, K8h, lane, y);
     {   // [policy logits 0..A-1 | value logits A..A+S-1]
         float mp = -__builtin_inff(), mv = -__builtin_inff();
 #pragma unroll

@@ -54,7 +54,7 @@ __device__ __forceinline__ void stage_pbc(double *pbc_lds, const Params &P, int 
 // policy / action when the launch acts, the stream position.  KS: expand_backup_tree's; out: the tree's head outputs (A policy
 // values | value | reward); stage: the tree's staged random words; rec: the tree's path records, in their place (path_col).
 // (The kernels that keep the path records in LDS and copy the last path back -- k_search_mlp, k_search_vision,
-// k_search_mlp_players -- have tails of their own: behind a helper their instruction counts change, see DESIGN.md 3.8.)
+// k_search_mlp_players -- have tails of their own: behind a helper their instruction counts change, see DESIGN.md 3.9.)
 template <int MAXA, int KS, class RNG, class REC>
 __device__ __forceinline__ void finish_tree(const Params &P, int tree, RNG &rng, TreeHdr &h, int packed, int sims, const uint32_t *stage,
                                             const float *out, int A, REC rec, const ActOut &act) {

@@ -269,6 +269,78 @@ class HipMlpTileHeads(FusedMlpHeads):
         return hidden, reward, policy, value
 
 
+class HipMlpLargeHeads(FusedMlpHeads):
+    """`mlp_model` heads for up to 1024 actions (H <= 128, 2 S <= 128, no limit on A + S): the recurrent networks as ONE
+    hand-written kernel per simulation round (smz_mlp_recurrent_large, csrc/smz_mlp_large.hip) on the parent's hidden row and
+    the action itself -- select writes no [B, S + A] one-hot input.  The packed image is that of smz_mlp_layout_large
+    (include/smz.h): the two input matrices as a hidden part + an action table, the two prediction output matrices as
+    128-column panels.  The root evaluation stays on the torch GEMMs of FusedMlpHeads (once per search).  Opt-in
+    (Muzero.heads(backend="large")).  Raises ValueError outside the kernel's limits."""
+    wants_mlp_input, wants_parent_hidden = False, True
+
+    def __init__(self, weights, dims, device):
+        super().__init__(weights, dims, device)
+        d = _lib.MlpDesc(int(dims["obs"]), self.A, self.S, self.H, self.L)
+        if not hasattr(self.lib, "smz_mlp_layout_large") or self.lib.smz_mlp_layout_large(C.byref(d)) != 0:
+            raise ValueError("mlp heads outside the limits of the large-action tile kernel (A <= 1024, H <= 128, 2 S <= 128)")
+        self.large_desc = d     # (not `desc` / `wide_desc`: those names mark heads a single-launch search kernel can take)
+        self.packed = torch.from_numpy(self.pack(weights, d)).to(self.device)
+
+    @staticmethod
+    def pack(weights, d):
+        """The float32 image smz_mlp_layout_large describes, from the torch-layout arrays ([O, K] weights)."""
+        import numpy as np
+        A, S, OP = d.A, d.S, d.OP
+        r8 = lambda k: (k + 7) & ~7
+        buf = np.zeros(d.total_floats, np.float32)
+
+        def wide(at, Wt):
+            """Wt [K, O <= OP] input-major -> the 4-way interleaved wide matrix at float offset `at`, K padded to 8."""
+            K, O = Wt.shape
+            P = np.zeros((r8(K), OP), np.float32)
+            P[:K, :O] = Wt
+            buf[at:at + P.size] = P.reshape(r8(K) // 4, 4, OP).transpose(0, 2, 1).reshape(-1)
+
+        for m, (name, parts) in enumerate(HipMlpHeads._MATS):
+            if "_mid" in name and d.L == 0:
+                continue
+            W = [np.asarray(weights[p + "_w"], np.float32) for p in parts]          # [O, K] each
+            b = [np.asarray(weights[p + "_b"], np.float32) for p in parts]
+            at, bias = d.off[m], d.off[15 + m]
+            if name in ("dyn_in", "ady_in"):            # hidden part, then the action table [A][OP]
+                Wt = W[0].T                             # [S + A, H]
+                wide(at, Wt[:S])
+                table = np.zeros((A, OP), np.float32)
+                table[:, :Wt.shape[1]] = Wt[S:]
+                buf[at + r8(S) * OP:at + (r8(S) + A) * OP] = table.reshape(-1)
+                buf[bias:bias + b[0].size] = b[0]
+            elif name in ("pre_out", "apr_out"):        # policy panels of OP columns, then the value panel
+                H = W[0].shape[1]
+                panels = (A + OP - 1) // OP
+                for p in range(panels):
+                    lo, hi = p * OP, min(A, (p + 1) * OP)
+                    wide(at + p * r8(H) * OP, W[0][lo:hi].T)
+                    buf[bias + p * OP:bias + p * OP + hi - lo] = b[0][lo:hi]
+                wide(at + panels * r8(H) * OP, W[1].T)
+                buf[bias + panels * OP:bias + panels * OP + S] = b[1]
+            else:
+                wide(at, np.concatenate(W, 0).T)
+                bb = np.concatenate(b, 0)
+                buf[bias:bias + bb.size] = bb
+        return buf
+
+    def recurrent(self, engine):
+        ph, branch = engine.parent_hidden, engine.branch
+        B = ph.shape[0]
+        assert ph.dtype == torch.float32 and ph.is_contiguous() and ph.shape[1] == self.S
+        hidden, reward = self._out("h", (B, self.S)), self._out("r", (B,))
+        policy, value = self._out("p", (B, self.A)), self._out("v", (B,))
+        _lib.check(self.lib.smz_mlp_recurrent_large(C.byref(self.large_desc), _ptr(self.packed), _ptr(ph), _ptr(engine.last_action),
+                                                    _ptr(branch), _ptr(hidden), _ptr(reward), _ptr(policy), _ptr(value), B,
+                                                    _stream(self.device)))
+        return hidden, reward, policy, value
+
+
 class HipVisionHeads:
     """`vision_model` heads (the reference's ResNet-v2 family, compat_vision.py) evaluated by hand-written HIP kernels:
     smz_vision_initial (one workgroup per frame) and smz_vision_recurrent (one wavefront per leaf).  Weights are

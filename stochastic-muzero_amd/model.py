@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import compat_lstm, compat_mlp, compat_vision
-from .heads import (MLP_ARRAYS, FusedMlpHeads, HipLstmHeads, HipMlpHeads, HipMlpTileHeads, HipVisionHeads, LstmTorchHeads,
+from .heads import (MLP_ARRAYS, FusedMlpHeads, HipLstmHeads, HipMlpHeads, HipMlpLargeHeads, HipMlpTileHeads, HipVisionHeads, LstmTorchHeads,
                     ModuleHeads)
 
 _FUNCS = ("representation", "prediction", "afterstate_prediction", "afterstate_dynamics", "dynamics", "encoder")
@@ -107,6 +107,7 @@ def mlp_arrays_from_modules(rep, pre, apr, ady, dyn):
 
 class Muzero:
     """Inference-side stand-in for the reference's Muzero object."""
+    heads_backend = "auto"      # what heads(backend=None) resolves to: the loops call heads(device) without a backend
 
     def __init__(self, model_structure="mlp_model", observation_space_dimensions=None, action_space_dimensions=None,
                  state_space_dimensions=9, hidden_layer_dimensions=16, number_of_hidden_layer=1, device="cpu",
@@ -275,17 +276,29 @@ class Muzero:
         self._heads = {}
         self._heads_version = {}
 
-    def heads(self, device, instance=0, backend="auto"):
+    def heads(self, device, instance=0, backend=None):
         """Batched evaluator on `device`.  backend: "hip" = the fused LDS-resident HIP kernels (mlp_model and lstm_model when
         the networks fit a CU's LDS; vision_model), "torch" = torch-ROCm GEMMs + HIP epilogues, "auto" = hip when possible,
-        else (mlp_model) the wide tile kernel for the recurrent networks when the shape is within its limits, else torch.
+        else (mlp_model) the wide tile kernel for the recurrent networks when the shape is within its limits, else torch;
+        "large" (mlp_model, opt-in) = the large-action tile kernel, up to 1024 actions (ValueError outside its limits);
+        None = self.heads_backend ("auto" unless set).
         `instance` distinguishes evaluators that must not share output buffers (one per concurrent stream group)."""
+        if backend is None:
+            backend = self.heads_backend
         key = (str(device), instance, backend)
         version = self.weights_version()
         if key in self._heads and self._heads_version.get(key) != version:
             del self._heads[key]              # the modules were updated in place (optimizer step, load_state_dict, ...)
         self._heads_version[key] = version
         if key not in self._heads:
+            if self.model_structure == "mlp_model" and backend == "large":
+                arrays = mlp_arrays_from_modules(self.representation_function, self.prediction_function,
+                                                 self.afterstate_prediction_function, self.afterstate_dynamics_function,
+                                                 self.dynamics_function)
+                dims = dict(obs=self.observation_dimension, A=self.action_dimension, S=self.state_dimension,
+                            H=self.hidden_layer_dimension, L=self.number_of_hidden_layer)
+                self._heads[key] = HipMlpLargeHeads(arrays, dims, device)
+                return self._heads[key]
             if self.model_structure == "mlp_model" and backend in ("auto", "hip"):
                 arrays = mlp_arrays_from_modules(self.representation_function, self.prediction_function,
                                                  self.afterstate_prediction_function, self.afterstate_dynamics_function,

@@ -503,7 +503,8 @@ int smz_mlp_recurrent_wide(const smz_mlp_desc *desc, const float *weights_dev, c
  *   off[10] pre_out, off[11] apr_out   P + 1 panels, P = ceil(A / 128), each a wide matrix of H rows (R8(H) x 128 floats):
  *                                  panel p < P holds policy columns 128 p .. min(A, 128 p + 128) - 1, panel P the S value columns
  *   off[15 + 10], off[15 + 11]     P + 1 bias vectors of 128 floats, one per panel
- *   every other matrix and bias    as smz_mlp_layout_wide lays it out (the representation matrices are present and unused)
+ *   every other matrix and bias    as smz_mlp_layout_wide lays it out (the representation matrices are present; they are unused
+ *                                  unless the root is evaluated by smz_mlp_initial_large)
  * total_floats = 128 * (2 (R8(S) + A) + 4 M + 3 R8(H) + 2 R8(S) + 2 (P + 1) R8(H) + R8(obs) + M + 13 + 2 (P + 1)), M = R8(H) if
  * number_of_hidden_layer > 0 else 0.
  * smz_mlp_recurrent_large: one launch, for every row the pair of networks its branch flag names (non-zero: dynamics +
@@ -517,6 +518,22 @@ int smz_mlp_layout_large(smz_mlp_desc *desc);
 int smz_mlp_recurrent_large(const smz_mlp_desc *desc, const float *weights_dev, const float *parent_hidden_dev,
                             const int32_t *last_action_dev, const uint8_t *branch_dev, float *hidden_out_dev,
                             float *reward_out_dev, float *policy_out_dev, float *value_out_dev, int B, smz_stream stream);
+
+/* The ROOT evaluation of those two families in one launch each (csrc/smz_mlp_root.hip): smz_mlp_initial on an image of
+ * smz_mlp_layout_wide (smz_mlp_initial_wide) or of smz_mlp_layout_large (smz_mlp_initial_large) -- representation +
+ * scale_to_bound_action + root prediction trunk + policy softmax: obs_dev [B,obs] -> hidden_out_dev [B,S] (scaled),
+ * policy_out_dev [B,A] (softmax; while smz_mlp_initial_large runs it also parks the logits there).  They read the rep_in /
+ * rep_mid / rep_out and pre_in / pre_mid / pre_out entries of the image, which stays as the layout functions describe it.
+ * 16-row tiles on the matrix cores, weights streamed from L2 (wide: one wavefront per tile; large: a workgroup of four
+ * wavefronts per tile, which share its policy panels); a row's outputs do not depend on the batch it is evaluated in.  No allocation, no host read: safe under stream capture.  Outputs agree with the float64
+ * evaluation of the networks within the tolerances of smz_mlp_recurrent_wide, not bit for bit with GEMM-based evaluations.
+ * SMZ_ERR_INVALID: a null pointer, B < 1, a descriptor the matching layout function would not produce (a wide descriptor
+ * handed to _large and the reverse included).  SMZ_ERR_TOO_LARGE: obs > 1024 (the observation tile of a wavefront lives in
+ * LDS).  Both are returned before any HIP call.  neural_network_mlp_model.py:5-83, muzero_model.py:802-842. */
+int smz_mlp_initial_wide(const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, float *hidden_out_dev,
+                         float *policy_out_dev, int B, smz_stream stream);
+int smz_mlp_initial_large(const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, float *hidden_out_dev,
+                          float *policy_out_dev, int B, smz_stream stream);
 
 /* ---- synthetic environment + trajectory record (self_play.py:63-98 loop body around the search) -------------- */
 /* CartPole-v1 shaped Euler step on device (float64 state, float32 observation), used for the synthetic

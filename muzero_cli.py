@@ -65,9 +65,13 @@ def mcts_kwargs(config, num_simulations=None):
 def set_heads_backend(model, config):
     """"large_action_heads": true in the monte_carlo_tree_search section (not a key of the reference's configs, and not an
     argument of BatchedMCTS: mcts_kwargs leaves it out) makes model.heads(device) hand out the large-action HIP heads
-    (Muzero.heads_backend = "large"); a config without the key leaves the model alone."""
+    (Muzero.heads_backend = "large"); a config without the key leaves the model alone.
+    "hip_root_evaluation": true in the same section (the same kind of key) makes the wide and the large-action HIP heads evaluate
+    the root in one HIP launch as well (Muzero.hip_root = True); every other evaluator ignores it."""
     if config["monte_carlo_tree_search"].get("large_action_heads"):
         model.heads_backend = "large"
+    if config["monte_carlo_tree_search"].get("hip_root_evaluation"):
+        model.hip_root = True
     return model
 
 

@@ -229,21 +229,52 @@ class HipMlpHeads:
         return hidden, reward, policy, value
 
 
+HIP_ROOT_MAX_OBS = 1024     # smz_mlp_initial_wide / _large: the observation tile of a wavefront lives in LDS
+
+
+class HipRootLimit(ValueError):
+    """hip_root=True asked for an observation wider than HIP_ROOT_MAX_OBS: an explicit opt-in never falls back."""
+
+
+def _check_hip_root(lib, obs, entry):
+    if not hasattr(lib, entry):
+        raise RuntimeError(f"libsmz.so does not export {entry} (hip_root=True needs it)")
+    if obs > HIP_ROOT_MAX_OBS:
+        raise HipRootLimit(f"hip_root=True: observations of {obs} floats exceed the limit of {HIP_ROOT_MAX_OBS} of {entry}")
+
+
+def _hip_initial(heads, entry, desc, obs):
+    """FusedMlpHeads.initial as ONE launch of `entry` on the packed image, into the same cached h0 / p0 buffers."""
+    B = obs.shape[0]
+    assert obs.dtype == torch.float32 and obs.is_contiguous() and obs.shape[1] == heads.obs
+    hidden, policy = heads._out("h0", (B, heads.S)), heads._out("p0", (B, heads.A))
+    _lib.check(getattr(heads.lib, entry)(C.byref(desc), _ptr(heads.packed), _ptr(obs), _ptr(hidden), _ptr(policy), B,
+                                         _stream(heads.device)))
+    return hidden, policy
+
+
 class HipMlpTileHeads(FusedMlpHeads):
     """`mlp_model` heads too wide for the LDS-resident kernels (H <= 128, 2 S <= 128, any number_of_hidden_layer: the
     reference's config 434, S 61 / H 126 / L 0, and its checkpoint 450, L 4): the recurrent networks as ONE hand-written kernel per simulation round
     (smz_mlp_recurrent_wide: 16-leaf tiles on the matrix cores, weights streamed from L2 in the 128-wide packed layout of
     smz_mlp_layout_wide) instead of ten library launches; the root evaluation stays on the torch GEMMs of FusedMlpHeads
-    (once per search).  Raises ValueError outside the kernel's limits."""
+    (once per search) unless hip_root=True (opt-in): then it is ONE launch on the same packed image (smz_mlp_initial_wide;
+    observations of up to 1024 floats, ValueError above), equal to the torch root within float32 rounding, not bit for bit.
+    Raises ValueError outside the kernel's limits."""
     wants_mlp_input, wants_parent_hidden = True, False
 
-    def __init__(self, weights, dims, device):
+    def __init__(self, weights, dims, device, hip_root=False):
         import numpy as np
         super().__init__(weights, dims, device)
+        self.hip_root = bool(hip_root)
         d = _lib.MlpDesc(int(dims["obs"]), self.A, self.S, self.H, self.L)
         if not hasattr(self.lib, "smz_mlp_layout_wide") or self.lib.smz_mlp_layout_wide(C.byref(d)) != 0:
             raise ValueError("mlp heads outside the limits of the wide tile kernel (use FusedMlpHeads)")
         self.wide_desc = d      # (not `desc`: that name marks heads the single-launch search kernel can take)
+        if self.hip_root:
+            _check_hip_root(self.lib, self.obs, "smz_mlp_initial_wide")
+            # (bound on the instance: without the flag `initial` stays FusedMlpHeads.initial itself)
+            self.initial = lambda obs: _hip_initial(self, "smz_mlp_initial_wide", self.wide_desc, obs)
         buf = np.zeros(d.total_floats, np.float32)
         OP = d.OP
         for m, (_, parts) in enumerate(HipMlpHeads._MATS):
@@ -274,16 +305,22 @@ class HipMlpLargeHeads(FusedMlpHeads):
     hand-written kernel per simulation round (smz_mlp_recurrent_large, csrc/smz_mlp_large.hip) on the parent's hidden row and
     the action itself -- select writes no [B, S + A] one-hot input.  The packed image is that of smz_mlp_layout_large
     (include/smz.h): the two input matrices as a hidden part + an action table, the two prediction output matrices as
-    128-column panels.  The root evaluation stays on the torch GEMMs of FusedMlpHeads (once per search).  Opt-in
-    (Muzero.heads(backend="large")).  Raises ValueError outside the kernel's limits."""
+    128-column panels.  The root evaluation stays on the torch GEMMs of FusedMlpHeads (once per search) unless
+    hip_root=True (opt-in): then it is ONE launch on the same packed image (smz_mlp_initial_large; observations of up to 1024
+    floats, ValueError above).  Opt-in (Muzero.heads(backend="large")).  Raises ValueError outside the kernel's limits."""
     wants_mlp_input, wants_parent_hidden = False, True
 
-    def __init__(self, weights, dims, device):
+    def __init__(self, weights, dims, device, hip_root=False):
         super().__init__(weights, dims, device)
+        self.hip_root = bool(hip_root)
         d = _lib.MlpDesc(int(dims["obs"]), self.A, self.S, self.H, self.L)
         if not hasattr(self.lib, "smz_mlp_layout_large") or self.lib.smz_mlp_layout_large(C.byref(d)) != 0:
             raise ValueError("mlp heads outside the limits of the large-action tile kernel (A <= 1024, H <= 128, 2 S <= 128)")
         self.large_desc = d     # (not `desc` / `wide_desc`: those names mark heads a single-launch search kernel can take)
+        if self.hip_root:
+            _check_hip_root(self.lib, self.obs, "smz_mlp_initial_large")
+            # (bound on the instance: without the flag `initial` stays FusedMlpHeads.initial itself)
+            self.initial = lambda obs: _hip_initial(self, "smz_mlp_initial_large", self.large_desc, obs)
         self.packed = torch.from_numpy(self.pack(weights, d)).to(self.device)
 
     @staticmethod

@@ -332,7 +332,8 @@ class BatchedMCTS(_Hyper):
             if self._try_single(eng, lambda: eng.search_lstm(heads.desc, heads.weights, hidden, policy, **kw), outside("lstm search")):
                 return eng
         elif single and self.wide_single_launch and isinstance(getattr(heads, "wide_desc", None), _lib.MlpDesc):
-            # wide mlp_model heads, opt-in: root evaluation (torch GEMMs), then the whole search in one launch
+            # wide mlp_model heads, opt-in: root evaluation (torch GEMMs, or one HIP launch for hip_root heads), then the whole search
+            # in one launch
             hidden, policy, eng = rooted()
             if self._try_single(eng, lambda: eng.search_mlp_wide(heads.wide_desc, heads.packed, hidden, policy, **kw),
                                 outside("wide mlp search")):

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import compat_lstm, compat_mlp, compat_vision
-from .heads import (MLP_ARRAYS, FusedMlpHeads, HipLstmHeads, HipMlpHeads, HipMlpLargeHeads, HipMlpTileHeads, HipVisionHeads, LstmTorchHeads,
+from .heads import (MLP_ARRAYS, FusedMlpHeads, HipLstmHeads, HipMlpHeads, HipMlpLargeHeads, HipMlpTileHeads, HipRootLimit, HipVisionHeads, LstmTorchHeads,
                     ModuleHeads)
 
 _FUNCS = ("representation", "prediction", "afterstate_prediction", "afterstate_dynamics", "dynamics", "encoder")
@@ -108,6 +108,7 @@ def mlp_arrays_from_modules(rep, pre, apr, ady, dyn):
 class Muzero:
     """Inference-side stand-in for the reference's Muzero object."""
     heads_backend = "auto"      # what heads(backend=None) resolves to: the loops call heads(device) without a backend
+    hip_root = False            # what heads(hip_root=None) resolves to: the root of the wide / large tile heads in HIP (opt-in)
 
     def __init__(self, model_structure="mlp_model", observation_space_dimensions=None, action_space_dimensions=None,
                  state_space_dimensions=9, hidden_layer_dimensions=16, number_of_hidden_layer=1, device="cpu",
@@ -276,16 +277,20 @@ class Muzero:
         self._heads = {}
         self._heads_version = {}
 
-    def heads(self, device, instance=0, backend=None):
+    def heads(self, device, instance=0, backend=None, hip_root=None):
         """Batched evaluator on `device`.  backend: "hip" = the fused LDS-resident HIP kernels (mlp_model and lstm_model when
         the networks fit a CU's LDS; vision_model), "torch" = torch-ROCm GEMMs + HIP epilogues, "auto" = hip when possible,
         else (mlp_model) the wide tile kernel for the recurrent networks when the shape is within its limits, else torch;
         "large" (mlp_model, opt-in) = the large-action tile kernel, up to 1024 actions (ValueError outside its limits);
         None = self.heads_backend ("auto" unless set).
+        hip_root (opt-in; None = self.hip_root, False unless set): the wide and the large tile heads evaluate the root in ONE
+        HIP launch too (smz_mlp_initial_wide / _large) instead of the torch GEMMs; every other evaluator ignores it.
         `instance` distinguishes evaluators that must not share output buffers (one per concurrent stream group)."""
         if backend is None:
             backend = self.heads_backend
-        key = (str(device), instance, backend)
+        if hip_root is None:
+            hip_root = self.hip_root
+        key = (str(device), instance, backend) + (("hip_root",) if hip_root else ())
         version = self.weights_version()
         if key in self._heads and self._heads_version.get(key) != version:
             del self._heads[key]              # the modules were updated in place (optimizer step, load_state_dict, ...)
@@ -297,7 +302,7 @@ class Muzero:
                                                  self.dynamics_function)
                 dims = dict(obs=self.observation_dimension, A=self.action_dimension, S=self.state_dimension,
                             H=self.hidden_layer_dimension, L=self.number_of_hidden_layer)
-                self._heads[key] = HipMlpLargeHeads(arrays, dims, device)
+                self._heads[key] = HipMlpLargeHeads(arrays, dims, device, hip_root=bool(hip_root))
                 return self._heads[key]
             if self.model_structure == "mlp_model" and backend in ("auto", "hip"):
                 arrays = mlp_arrays_from_modules(self.representation_function, self.prediction_function,
@@ -312,8 +317,10 @@ class Muzero:
                     if backend == "hip":
                         raise
                 try:        # too wide for LDS residency: tiles on the matrix cores with the weights streamed from L2
-                    self._heads[key] = HipMlpTileHeads(arrays, dims, device)
+                    self._heads[key] = HipMlpTileHeads(arrays, dims, device, hip_root=bool(hip_root))
                     return self._heads[key]
+                except HipRootLimit:
+                    raise       # (an explicit opt-in does not fall back)
                 except ValueError:
                     pass
             if self.model_structure == "mlp_model":

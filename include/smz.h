@@ -93,7 +93,8 @@ int smz_create(const smz_config *cfg, smz_handle **out);
 /* [sync] The same handle for 1 <= num_actions <= SMZ_MAX_ACTIONS_LARGE (SMZ_ERR_INVALID outside): the step-wise calls
  * (smz_root_init, smz_select, smz_expand_backup(_select), smz_act) run kernels with one wavefront per tree and the A-wide
  * arrays in LDS; results, tree layout and random-word consumption are those of an smz_create handle.  The single-launch
- * searches (smz_search_mlp*, smz_search_vision*, smz_search_lstm*, smz_search_mlp_wide*) and smz_enable_stats return SMZ_ERR_TOO_LARGE on such a handle.  Path
+ * searches (smz_search_mlp*, smz_search_vision*, smz_search_lstm*, smz_search_mlp_wide*) and smz_enable_stats return SMZ_ERR_TOO_LARGE on such a handle
+ * -- all but smz_search_mlp_large(_act), the single launch of exactly these handles.  Path
  * records name a child as (block << 10 | slot) instead of (block << 8 | slot); smz_debug_dump_tree decodes either. */
 int smz_create_large_actions(const smz_config *cfg, smz_handle **out);
 /* [sync] */
@@ -143,8 +144,8 @@ int smz_set_active(smz_handle *h, const uint8_t *active_dev);
  * at depth d plays cycle index (root + 2 (d >> 2) + ((d & 3) != 0)) mod n_cycle; the backup adds -value instead of value to
  * the value_sum of every node whose cycle VALUE differs from the root's.  Selection, the random draws and the value chain
  * are unchanged.  n_cycle > 1 selects the multi-player step-wise kernels (smz_expand_backup / smz_expand_backup_select);
- * the single-launch searches (smz_search_mlp*, smz_search_vision*, smz_search_lstm*, smz_search_mlp_wide*) then fail with SMZ_ERR_INVALID
- * -- all but smz_search_mlp_players(_act), the single launch of exactly these handles.  n_cycle = 1 restores
+ * the single-launch searches (smz_search_mlp*, smz_search_vision*, smz_search_lstm*, smz_search_mlp_wide*, smz_search_mlp_large*) then
+ * fail with SMZ_ERR_INVALID -- all but smz_search_mlp_players(_act), the single launch of exactly these handles.  n_cycle = 1 restores
  * the single-player search (cycle_values_host may then be NULL). */
 int smz_set_players(smz_handle *h, int n_cycle, const float *cycle_values_host, const int32_t *root_player_dev);
 /* Large batches: the row moves of a simulation round can be left to the network kernel.  When ids_dev is set, every
@@ -449,6 +450,32 @@ int smz_search_mlp_wide_act(smz_handle *h, const smz_mlp_desc *desc, const float
                             const float *policy0_dev, int train, double temperature, const double *pow_table_host,
                             int32_t *action_dev, double *policy_dev, double *child_visits_dev, float *root_value_dev,
                             smz_stream stream);
+
+/* The same for a LARGE-ACTION handle (smz_create_large_actions: up to SMZ_MAX_ACTIONS_LARGE actions) and the large-action
+ * `mlp_model` image (a descriptor of smz_mlp_layout_large; opt-in: BatchedMCTS(large_single_launch=True)).  The root's hidden state
+ * and policy come from the heads' root evaluation (hidden0_dev [B,S], policy0_dev [B,A]).  The root is built by the step-wise root
+ * kernels (one launch, two when training: the Dirichlet noise), all num_simulations rounds run as ONE launch of
+ * k_search_mlp_large<PHX> (none with num_simulations == 0), and the `_act` form adds the step-wise act kernel: 2-4 launches instead
+ * of 2 + 3 x num_simulations.  A workgroup of 4 wavefronts owns T = ceil(B / 256) trees, at most those whose LDS map fits 160 KB
+ * (4 up to 768 actions, 3 above; the environment variable SMZ_LARGE_SEARCH_T, 1 .. 4, replaces the count: the results do not
+ * depend on it), a wavefront per tree with the tree code of the step-wise kernels (same device functions) and the tree's
+ * MT19937 words in LDS for the whole search; once per round the four wavefronts evaluate the workgroup's <= T leaves per branch
+ * through the tile body of k_mlp_recurrent_large_split (same device function, same compiler flags).  Policies pass through
+ * [B][A] work rows the handle allocates on the first call.  Trees, root statistics, hidden rows and stream positions equal the
+ * step-wise calls bit for bit wherever smz_mlp_recurrent_large runs its split geometry (up to 2048 trees at A <= 128, up to 4096
+ * above); beyond, the step-wise head kernel sums the policy panels in another order and the policies may differ in their last
+ * float32 bits.  SMZ_ERR_INVALID: a null argument, a handle that is not a large-action handle, a multi-player handle, a descriptor
+ * smz_mlp_layout_large would not produce, desc->A / desc->S other than the handle's.  SMZ_ERR_TOO_LARGE: an LDS map above 160 KB
+ * (none within SMZ_MAX_ACTIONS_LARGE).  MT19937 and Philox handles alike; smz_set_active is honoured.  The first call allocates
+ * (not legal under stream capture); a new `_act` temperature is a synchronous upload, as for smz_act.
+ * monte_carlo_tree_search.py:311-349. */
+int smz_search_mlp_large(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *hidden0_dev,
+                         const float *policy0_dev, int train, smz_stream stream);
+/* ... followed by smz_act as a launch of its own behind the rounds. */
+int smz_search_mlp_large_act(smz_handle *h, const smz_mlp_desc *desc, const float *weights_dev, const float *hidden0_dev,
+                             const float *policy0_dev, int train, double temperature, const double *pow_table_host,
+                             int32_t *action_dev, double *policy_dev, double *child_visits_dev, float *root_value_dev,
+                             smz_stream stream);
 
 /* smz_search_mlp for a MULTI-PLAYER handle (smz_set_players with n_cycle > 1; opt-in: BatchedMCTS(players_single_launch=True)):
  * the whole search of every tree in one launch, with the signed backup of mcts:299-308.  Same arguments and the same networks as

@@ -57,6 +57,8 @@ def mcts_kwargs(config, num_simulations=None):
         kw["lstm_single_launch"] = bool(m["lstm_single_launch"])
     if "wide_single_launch" in m:       # (not a key of the reference's configs) wide mlp_model searches in one launch: BatchedMCTS
         kw["wide_single_launch"] = bool(m["wide_single_launch"])
+    if "large_single_launch" in m:      # (not a key of the reference's configs) large-action mlp_model searches in one launch
+        kw["large_single_launch"] = bool(m["large_single_launch"])
     if "players_single_launch" in m:    # (not a key of the reference's configs) multi-player mlp_model searches in one launch: BatchedMCTS
         kw["players_single_launch"] = bool(m["players_single_launch"])
     return kw

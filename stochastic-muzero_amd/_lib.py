@@ -126,6 +126,8 @@ SIGNATURES = {
     "smz_search_lstm_act": (C.c_int, [_P, C.POINTER(LstmDesc), _P, _P, _P, C.c_int, C.c_double, _P, _P, _P, _P, _P, _P]),
     "smz_search_mlp_wide": (C.c_int, [_P, C.POINTER(MlpDesc), _P, _P, _P, C.c_int, _P]),
     "smz_search_mlp_wide_act": (C.c_int, [_P, C.POINTER(MlpDesc), _P, _P, _P, C.c_int, C.c_double, _P, _P, _P, _P, _P, _P]),
+    "smz_search_mlp_large": (C.c_int, [_P, C.POINTER(MlpDesc), _P, _P, _P, C.c_int, _P]),
+    "smz_search_mlp_large_act": (C.c_int, [_P, C.POINTER(MlpDesc), _P, _P, _P, C.c_int, C.c_double, _P, _P, _P, _P, _P, _P]),
     "smz_search_mlp_players": (C.c_int, [_P, C.POINTER(MlpDesc), _P, _P, C.c_int, _P]),
     "smz_search_mlp_players_act": (C.c_int, [_P, C.POINTER(MlpDesc), _P, _P, C.c_int, C.c_double, _P, _P, _P, _P, _P, _P]),
     "smz_cartpole_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P]),

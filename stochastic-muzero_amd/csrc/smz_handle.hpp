@@ -24,6 +24,7 @@ struct smz_handle {
     char last_kernel[96];      // the single-launch search instantiation launched last, as rocprofv3 prints it (smz_last_kernel)
     uint32_t *d_player_neg;    // [SMZ_MAX_PLAYER_CYCLE] sign masks of smz_set_players (allocated by its first multi-player call)
     bool large_actions;        // smz_create_large_actions: the step-wise calls run the wave-per-tree kernels (smz_large_actions.hip)
+    float *d_la_policy;        // [B][A] policy work rows of smz_search_mlp_large (allocated by its first call)
 };
 
 // the last-error text: defined in smz_kernels.hip

@@ -363,6 +363,7 @@ int create_handle(const smz_config *cfg, smz_handle **out, bool large_actions) {
     h->pow_valid = false;
     h->d_player_neg = nullptr;
     h->large_actions = large_actions;
+    h->d_la_policy = nullptr;
     h->pow_T = 0.0;
     h->stats_on = false;
 

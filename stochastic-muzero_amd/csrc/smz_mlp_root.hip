@@ -14,7 +14,7 @@
 //   * wide policy: one wide_layer over pre_out [policy | value], softmax over the columns < A (the tail of wide_tile without its
 //     value half).
 //   * large policy: the ceil(A / 128) policy panels with the running-maximum / running-sum softmax, logits parked in policy_out.
-//     These are COPIES of the panel statements of large_tile (smz_mlp_large.hip), not a shared function: large_tile stays as it
+//     These are COPIES of the panel statements of large_tile (smz_mlp_large_device.hpp), not a shared function: large_tile stays as it
 //     is, so the two k_mlp_recurrent_large* kernels cannot move by an instruction, and the copy drops what the root does not
 //     need (the action table, the value panel, the choice of PARTS).
 // Geometry, one per layout, the same for every batch size (a row's outputs depend neither on its tile mates nor on the batch):
@@ -36,6 +36,7 @@
 #include "../../include/smz.h"
 #include "smz_mlp_device.hpp"
 #include "smz_mlp_wide_device.hpp"
+#include "smz_mlp_large_device.hpp"          // r8
 
 using namespace smz_mlp;
 
@@ -46,7 +47,6 @@ constexpr int kRootMaxObs = 1024;            // widest observation row: a 64 KB 
 constexpr int kRootMaxWgs = 2048;            // grid cap; more tiles than the grid takes in one trip grid-stride
 constexpr int kRootLdsBytes = 160 * 1024;
 
-__host__ __device__ inline int r8(int k) { return (k + 7) & ~7; }
 __host__ __device__ inline int root_tile_floats(int obs) {
     const int f = kTileLeaves * r8(obs);
     return f > kWideTileFloats ? f : kWideTileFloats;

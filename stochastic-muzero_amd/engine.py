@@ -279,6 +279,12 @@ class SearchEngine:
         hidden0 [B,S] / policy0 [B,A] are the outputs of the heads' initial().  `act_temperature` as in search_mlp."""
         self._launch_search("smz_search_mlp_wide", wide_desc, packed, self._root(hidden0, policy0), train, act_temperature)
 
+    def search_mlp_large(self, large_desc, packed, hidden0, policy0, train=True, act_temperature=None):
+        """The rounds of a whole search in one launch for a large-action engine and the large-action `mlp_model` heads
+        (smz_search_mlp_large; HipMlpLargeHeads.large_desc / .packed): hidden0 [B,S] / policy0 [B,A] are the outputs of the heads'
+        initial().  `act_temperature` as in search_mlp (the action selection is a launch of its own behind the rounds)."""
+        self._launch_search("smz_search_mlp_large", large_desc, packed, self._root(hidden0, policy0), train, act_temperature)
+
     def search_mlp_players(self, mlp_desc, weights, obs, train=True, act_temperature=None):
         """Whole search in one launch for a multi-player engine (set_players with more than one cycle entry) and LDS-resident
         mlp_model heads (smz_search_mlp_players).  The root players are what `self.root_player` holds (set_root_player).

@@ -316,7 +316,7 @@ class HipMlpLargeHeads(FusedMlpHeads):
         d = _lib.MlpDesc(int(dims["obs"]), self.A, self.S, self.H, self.L)
         if not hasattr(self.lib, "smz_mlp_layout_large") or self.lib.smz_mlp_layout_large(C.byref(d)) != 0:
             raise ValueError("mlp heads outside the limits of the large-action tile kernel (A <= 1024, H <= 128, 2 S <= 128)")
-        self.large_desc = d     # (not `desc` / `wide_desc`: those names mark heads a single-launch search kernel can take)
+        self.large_desc = d     # (not `desc` / `wide_desc`: those mark heads of other single-launch kernels; this one marks smz_search_mlp_large's)
         if self.hip_root:
             _check_hip_root(self.lib, self.obs, "smz_mlp_initial_large")
             # (bound on the instance: without the flag `initial` stays FusedMlpHeads.initial itself)

@@ -133,7 +133,7 @@ class BatchedMCTS(_Hyper):
                  root_exploration_fraction=0.25, num_simulations=10, maxium_action_sample=2, number_of_player=1,
                  custom_loop=None, device=None, use_graph=True, fused=True, single_launch=True,
                  rng_mode=_lib.RNG_MT19937_NUMPY, lstm_single_launch=False, wide_single_launch=False,
-                 players_single_launch=False):
+                 players_single_launch=False, large_single_launch=False):
         self._set_hyper(pb_c_base, pb_c_init, discount, root_dirichlet_alpha, root_exploration_fraction,
                         num_simulations, maxium_action_sample, number_of_player, custom_loop)
         self.num_trees = int(num_trees)
@@ -156,6 +156,10 @@ class BatchedMCTS(_Hyper):
         # smz_search_mlp_players launch (opt-in: its rate against the step-wise graph is in DESIGN.md 3.7; both paths give the same
         # search, bit for bit)
         self.players_single_launch = bool(players_single_launch)
+        # large-action mlp_model heads (HipMlpLargeHeads, 33-1024 actions) search step-wise unless this is set: then heads.initial,
+        # the root kernels and ONE smz_search_mlp_large launch for all rounds (opt-in: its rate against the step-wise graph is in
+        # DESIGN.md 3.10; both paths give the same search, bit for bit, wherever the step-wise heads use their split geometry)
+        self.large_single_launch = bool(large_single_launch)
         self.engine = None
         self._to_play = None
         self._graph = None
@@ -312,7 +316,13 @@ class BatchedMCTS(_Hyper):
                                     outside("multi-player search")):
                     return eng
         elif int(getattr(heads, "A", 0)) > _lib.MAX_ACTIONS:
-            pass       # more actions than the per-lane kernels take: the wave-per-tree step-wise kernels (no single launch)
+            # more actions than the per-lane kernels take: the wave-per-tree step-wise kernels, or (opt-in, HipMlpLargeHeads) the
+            # single launch built for these handles; any other heads search step-wise, without a warning
+            if single and self.large_single_launch and isinstance(getattr(heads, "large_desc", None), _lib.MlpDesc):
+                hidden, policy, eng = rooted()
+                if self._try_single(eng, lambda: eng.search_mlp_large(heads.large_desc, heads.packed, hidden, policy, **kw),
+                                    outside("large-action search")):
+                    return eng
         elif single and isinstance(desc, _lib.MlpDesc):
             eng = self._ensure_engine(heads.A, heads.S)
             if self._try_single(eng, lambda: eng.search_mlp(heads.desc, heads.weights, observations,

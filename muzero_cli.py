@@ -53,14 +53,11 @@ def mcts_kwargs(config, num_simulations=None):
               num_simulations=m["num_simulations"] if num_simulations is None else num_simulations,
               maxium_action_sample=m["maxium_action_sample"], number_of_player=m["number_of_player"],
               custom_loop=m["custom_loop"])
-    if "lstm_single_launch" in m:       # (not a key of the reference's configs) lstm_model searches in one launch: BatchedMCTS
-        kw["lstm_single_launch"] = bool(m["lstm_single_launch"])
-    if "wide_single_launch" in m:       # (not a key of the reference's configs) wide mlp_model searches in one launch: BatchedMCTS
-        kw["wide_single_launch"] = bool(m["wide_single_launch"])
-    if "large_single_launch" in m:      # (not a key of the reference's configs) large-action mlp_model searches in one launch
-        kw["large_single_launch"] = bool(m["large_single_launch"])
-    if "players_single_launch" in m:    # (not a key of the reference's configs) multi-player mlp_model searches in one launch: BatchedMCTS
-        kw["players_single_launch"] = bool(m["players_single_launch"])
+    # (not keys of the reference's configs) the opt-in single-launch searches of BatchedMCTS: lstm_model, wide mlp_model,
+    # large-action mlp_model and multi-player mlp_model
+    for key in ("lstm_single_launch", "wide_single_launch", "large_single_launch", "players_single_launch"):
+        if key in m:
+            kw[key] = bool(m[key])
     return kw
 
 

@@ -47,6 +47,9 @@ class SearchEngine:
         self.cfg = _lib.Config(self.B, self.A, int(maxium_action_sample), self.S, self.sims, int(pb_c_base),
                                float(pb_c_init), float(discount), float(root_dirichlet_alpha),
                                float(root_exploration_fraction), int(rng_mode), int(self.device.index))
+        # set by set_active / the search launches / set_players / enable_leaf_ids
+        self._active = self._act_done = self.root_player = self.leaf_ids = None
+        self.n_cycle = 1
         h = C.c_void_p()
         self.large_actions = bool(large_actions)
         create = self.lib.smz_create_large_actions if self.large_actions else self.lib.smz_create
@@ -103,7 +106,7 @@ class SearchEngine:
         every node whose player's value differs from the root's (mcts:299-308).  The root player of every tree is read from
         `self.root_player` (int32 [B], engine-owned, so a captured graph stays valid while set_root_player rewrites it)."""
         vals = np.ascontiguousarray(cycle_values, dtype=np.float32).reshape(-1)
-        if len(vals) > 1 and getattr(self, "root_player", None) is None:
+        if len(vals) > 1 and self.root_player is None:
             self.root_player = torch.zeros(self.B, dtype=torch.int32, device=self.device)
         _lib.check(self.lib.smz_set_players(self.h, len(vals), vals.ctypes.data_as(C.c_void_p),
                                             _ptr(self.root_player) if len(vals) > 1 else None))
@@ -114,7 +117,7 @@ class SearchEngine:
     def set_root_player(self, to_play):
         """Root player index per tree (an int, a host array or a device tensor of B entries), copied into `self.root_player`
         on the current stream."""
-        if getattr(self, "n_cycle", 1) <= 1:
+        if self.n_cycle <= 1:
             raise RuntimeError("set_root_player needs a multi-player engine (set_players with more than one player)")
         if torch.is_tensor(to_play):
             src = to_play.reshape(-1).to(device=self.device, dtype=torch.int32)
@@ -130,7 +133,7 @@ class SearchEngine:
         """smz_set_leaf_ids_out: every selection also writes (leaf node id, parent node id) per tree to `self.leaf_ids`
         [B,2] int32, so that a network kernel can take and put its rows in the tree's own hidden-state storage
         (heads.HipMlpHeads at large batches) and the tree kernels move no rows."""
-        if on and getattr(self, "leaf_ids", None) is None:
+        if on and self.leaf_ids is None:
             self.leaf_ids = torch.full((self.B, 2), -1, dtype=torch.int32, device=self.device)
         if not on:
             self.leaf_ids = None
@@ -299,7 +302,7 @@ class SearchEngine:
     def act(self, temperature):
         """Game.policy_step's policy/action + store_search_statistics (game.py:179-235) for every tree."""
         temperature = float(temperature)
-        if getattr(self, "_act_done", None) == temperature:      # already computed in the tail of the search launch
+        if self._act_done == temperature:      # already computed in the tail of the search launch
             self._act_done = None
             return self.action, self.policy, self.child_visits, self.root_value
         self._act_done = None

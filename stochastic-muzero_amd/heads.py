@@ -43,14 +43,73 @@ def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-class FusedMlpHeads:
+class Heads:
+    """What every evaluator shares: the library, the device and the cached output buffers.  A class that a single-launch
+    search kernel can take names that kernel's kind in `single_launch` and hands it `single_launch_image()`."""
+    single_launch = None        # "mlp", "vision", "lstm", "wide" or "large" (BatchedMCTS.run); None: step-wise searches only
+
+    def __init__(self, device):
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        self._buf = {}
+
+    def _out(self, name, shape, dtype=torch.float32):
+        t = self._buf.get(name)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = self._buf[name] = torch.empty(*shape, dtype=dtype, device=self.device)
+        return t
+
+    def _round_out(self, B, hidden=True):
+        """The outputs of one round: hidden' [B,S] (None unless `hidden`), reward [B], policy [B,A], value [B].  The names are
+        fixed: a captured graph holds the buffers' addresses."""
+        return (self._out("h", (B, self.S)) if hidden else None, self._out("r", (B,)), self._out("p", (B, self.A)),
+                self._out("v", (B,)))
+
+    def single_launch_image(self):
+        """(descriptor, packed weights) of the single-launch search kernel of this kind."""
+        return self.desc, self.weights
+
+
+def interleave(Wt, width, pad):
+    """Wt [K, O <= width] (input-major) -> the flat float32 matrix the kernels read: K padded with zero rows to a multiple of
+    `pad` (4 or 8), rows padded with zero columns to `width`, four inputs interleaved -- element (k, o) at
+    ((k / 4) * width + o) * 4 + k % 4 (include/smz.h)."""
+    import numpy as np
+    K, O = Wt.shape
+    P = np.zeros(((K + pad - 1) // pad * pad, width), np.float32)
+    P[:K, :O] = Wt
+    return P.reshape(-1, 4, width).transpose(0, 2, 1).reshape(-1)
+
+
+# off[] order of smz_mlp_desc: (name of the input-major matrix, [names of the output heads concatenated])
+_MATS = [("dyn_in", ["dyn_in"]), ("ady_in", ["ady_in"]), ("dyn_mid", ["dyn_mid"]), ("ady_mid", ["ady_mid"]),
+         ("dyn_out", ["dyn_rw", "dyn_st"]), ("ady_out", ["ady_st"]), ("pre_in", ["pre_in"]), ("apr_in", ["apr_in"]),
+         ("pre_mid", ["pre_mid"]), ("apr_mid", ["apr_mid"]), ("pre_out", ["pre_pol", "pre_val"]),
+         ("apr_out", ["apr_pol", "apr_val"]), ("rep_in", ["rep_in"]), ("rep_mid", ["rep_mid"]), ("rep_out", ["rep_out"])]
+
+
+def pack_mats(weights, d, pad):
+    """The float32 image of smz_mlp_layout (pad 4) / smz_mlp_layout_wide (pad 8) from the torch-layout arrays ([O, K] weights):
+    every matrix of _MATS interleaved at d.off[m], its bias at d.off[15 + m]."""
+    import numpy as np
+    buf = np.zeros(d.total_floats, np.float32)
+    for m, (name, parts) in enumerate(_MATS):
+        if "_mid" in name and d.L == 0:
+            continue
+        W = interleave(np.concatenate([np.asarray(weights[p + "_w"], np.float32) for p in parts], 0).T, d.OP, pad)
+        b = np.concatenate([np.asarray(weights[p + "_b"], np.float32) for p in parts], 0)
+        buf[d.off[m]:d.off[m] + W.size] = W
+        buf[d.off[15 + m]:d.off[15 + m] + b.size] = b
+    return buf
+
+
+class FusedMlpHeads(Heads):
     wants_mlp_input, wants_parent_hidden = True, False
 
     def __init__(self, weights, dims, device):
         """weights: dict name -> array-like ('rep_in_w', 'rep_in_b', ...); dims: obs, A, S, H, L."""
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        self.obs, self.A, self.S, self.H, self.L = (int(dims[k]) for k in ("obs", "A", "S", "H", "L"))
+        super().__init__(device)
+        self.obs,self.A, self.S, self.H, self.L = (int(dims[k]) for k in ("obs", "A", "S", "H", "L"))
         w = {k: torch.as_tensor(v, dtype=torch.float32).to(self.device) for k, v in weights.items()}
         self.w = w
         A, S, H = self.A, self.S, self.H
@@ -81,7 +140,6 @@ class FusedMlpHeads:
                         torch.cat([z(A, H), w["apr_pol_w"]], 1), torch.cat([z(S, H), w["apr_val_w"]], 1)], 0)
         self.prd_out = (w3.t().contiguous(),
                         torch.cat([w["pre_pol_b"], w["pre_val_b"], w["apr_pol_b"], w["apr_val_b"]]))
-        self._buf = {}
 
     @classmethod
     def from_npz(cls, path, device):
@@ -90,12 +148,6 @@ class FusedMlpHeads:
         dims = {k: int(z["dim_" + k]) for k in ("obs", "A", "S", "H", "L")}
         weights = {n + s: z[n + s] for n in MLP_ARRAYS for s in ("_w", "_b")}
         return cls(weights, dims, device)
-
-    def _out(self, name, shape, dtype=torch.float32):
-        t = self._buf.get(name)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = self._buf[name] = torch.empty(*shape, dtype=dtype, device=self.device)
-        return t
 
     @staticmethod
     def _trunk(x, layers):
@@ -122,12 +174,11 @@ class FusedMlpHeads:
         smz_expand_backup takes."""
         x, branch = engine.mlp_input, engine.branch
         B, A, S = x.shape[0], self.A, self.S
+        hidden, reward, policy, value = self._round_out(B)
         t = F.elu(torch.addmm(self.dyn_in[1], x, self.dyn_in[0]))
         for _ in range(self.L):
             t = F.elu(torch.addmm(self.dyn_mid[1], t, self.dyn_mid[0]))
         o = torch.addmm(self.dyn_out[1], t, self.dyn_out[0])                                 # [B, 3S]
-        hidden = self._out("h", (B, S))
-        reward = self._out("r", (B,))
         fs = o.element_size()
         base = o.data_ptr()
         _lib.check(self.lib.smz_dynamics_epilogue(C.c_void_p(base + S * fs), C.c_void_p(base + 2 * S * fs),
@@ -137,8 +188,6 @@ class FusedMlpHeads:
         for _ in range(self.L):
             u = F.elu(torch.addmm(self.prd_mid[1], u, self.prd_mid[0]))
         q = torch.addmm(self.prd_out[1], u, self.prd_out[0])                                 # [B, 2A+2S]
-        policy = self._out("p", (B, A))
-        value = self._out("v", (B,))
         qb = q.data_ptr()
         _lib.check(self.lib.smz_prediction_epilogue(C.c_void_p(qb), C.c_void_p(qb + A * fs), C.c_void_p(qb + (A + S) * fs),
                                                     C.c_void_p(qb + (2 * A + S) * fs), 2 * A + 2 * S, _ptr(branch), A, S,
@@ -146,50 +195,24 @@ class FusedMlpHeads:
         return hidden, reward, policy, value
 
 
-class HipMlpHeads:
+class HipMlpHeads(Heads):
     """`mlp_model` heads evaluated by ONE hand-written HIP kernel per phase (smz_mlp_initial / smz_mlp_recurrent):
     weights packed once into the LDS layout described in include/smz.h, no library GEMMs, no torch ops.
     Raises ValueError when the networks do not fit a CU's LDS (use FusedMlpHeads then)."""
     wants_mlp_input, wants_parent_hidden = True, False
+    single_launch = "mlp"
     IN_PLACE_MIN = 8192       # from this many trees on (shipped network shape) the rows stay in the tree: see bind_engine
-    # off[] order of smz_mlp_desc: (name of the input-major matrix, [names of the output heads concatenated])
-    _MATS = [("dyn_in", ["dyn_in"]), ("ady_in", ["ady_in"]), ("dyn_mid", ["dyn_mid"]), ("ady_mid", ["ady_mid"]),
-             ("dyn_out", ["dyn_rw", "dyn_st"]), ("ady_out", ["ady_st"]), ("pre_in", ["pre_in"]), ("apr_in", ["apr_in"]),
-             ("pre_mid", ["pre_mid"]), ("apr_mid", ["apr_mid"]), ("pre_out", ["pre_pol", "pre_val"]),
-             ("apr_out", ["apr_pol", "apr_val"]), ("rep_in", ["rep_in"]), ("rep_mid", ["rep_mid"]), ("rep_out", ["rep_out"])]
+    _MATS = _MATS
 
     def __init__(self, weights, dims, device):
-        import numpy as np
-        self.lib = _lib.load()
-        self.device = torch.device(device)
+        super().__init__(device)
         self.obs, self.A, self.S, self.H, self.L = (int(dims[k]) for k in ("obs", "A", "S", "H", "L"))
         d = _lib.MlpDesc(self.obs, self.A, self.S, self.H, self.L)
         if self.lib.smz_mlp_layout(C.byref(d)) != 0:
             raise ValueError("mlp heads do not fit the LDS-resident kernel (use FusedMlpHeads)")
         self.desc = d
-        buf = np.zeros(d.total_floats, np.float32)
-        OP = d.OP
-        for m, (_, parts) in enumerate(self._MATS):
-            if "_mid" in parts[0] and self.L == 0:
-                continue
-            W = np.concatenate([np.asarray(weights[p + "_w"], np.float32) for p in parts], 0)      # [O, K] (torch layout)
-            b = np.concatenate([np.asarray(weights[p + "_b"], np.float32) for p in parts], 0)
-            O, K = W.shape
-            K4 = (K + 3) & ~3
-            blk = np.zeros((K4 // 4, OP, 4), np.float32)
-            Wt = np.zeros((K4, OP), np.float32)
-            Wt[:K, :O] = W.T
-            blk[:] = Wt.reshape(K4 // 4, 4, OP).transpose(0, 2, 1)
-            buf[d.off[m]:d.off[m] + K4 * OP] = blk.reshape(-1)
-            buf[d.off[15 + m]:d.off[15 + m] + O] = b
-        self.weights = torch.from_numpy(buf).to(self.device)
-        self._buf = {}
-
-    def _out(self, name, shape, dtype=torch.float32):
-        t = self._buf.get(name)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = self._buf[name] = torch.empty(*shape, dtype=dtype, device=self.device)
-        return t
+        self.weights = torch.from_numpy(pack_mats(weights, d, 4)).to(self.device)
+        self._in_place = None
 
     def initial(self, obs):
         B = obs.shape[0]
@@ -213,9 +236,9 @@ class HipMlpHeads:
         return dict(want_mlp_input=not in_place, want_parent_hidden=False)
 
     def recurrent(self, engine):
-        in_place = getattr(self, "_in_place", None) is engine
+        in_place = self._in_place is engine
         B = engine.B if in_place else engine.mlp_input.shape[0]
-        reward, policy, value = self._out("r", (B,)), self._out("p", (B, self.A)), self._out("v", (B,))
+        hidden, reward, policy, value = self._round_out(B, hidden=not in_place)     # (in place: the rows stay in the tree)
         if in_place:
             base, n, hs = engine.hidden_layout()
             _lib.check(self.lib.smz_mlp_recurrent_rows(C.byref(self.desc), _ptr(self.weights), base, n, hs, _ptr(engine.leaf_ids),
@@ -223,7 +246,6 @@ class HipMlpHeads:
                                                        _ptr(value), B, _stream(self.device)))
             return None, reward, policy, value
         x, branch = engine.mlp_input, engine.branch
-        hidden = self._out("h", (B, self.S))
         _lib.check(self.lib.smz_mlp_recurrent(C.byref(self.desc), _ptr(self.weights), _ptr(x), _ptr(branch), _ptr(hidden),
                                               _ptr(reward), _ptr(policy), _ptr(value), B, _stream(self.device)))
         return hidden, reward, policy, value
@@ -262,39 +284,28 @@ class HipMlpTileHeads(FusedMlpHeads):
     observations of up to 1024 floats, ValueError above), equal to the torch root within float32 rounding, not bit for bit.
     Raises ValueError outside the kernel's limits."""
     wants_mlp_input, wants_parent_hidden = True, False
+    single_launch = "wide"
 
     def __init__(self, weights, dims, device, hip_root=False):
-        import numpy as np
         super().__init__(weights, dims, device)
         self.hip_root = bool(hip_root)
         d = _lib.MlpDesc(int(dims["obs"]), self.A, self.S, self.H, self.L)
         if not hasattr(self.lib, "smz_mlp_layout_wide") or self.lib.smz_mlp_layout_wide(C.byref(d)) != 0:
             raise ValueError("mlp heads outside the limits of the wide tile kernel (use FusedMlpHeads)")
-        self.wide_desc = d      # (not `desc`: that name marks heads the single-launch search kernel can take)
+        self.wide_desc = d
         if self.hip_root:
             _check_hip_root(self.lib, self.obs, "smz_mlp_initial_wide")
             # (bound on the instance: without the flag `initial` stays FusedMlpHeads.initial itself)
             self.initial = lambda obs: _hip_initial(self, "smz_mlp_initial_wide", self.wide_desc, obs)
-        buf = np.zeros(d.total_floats, np.float32)
-        OP = d.OP
-        for m, (_, parts) in enumerate(HipMlpHeads._MATS):
-            if "_mid" in parts[0] and self.L == 0:
-                continue
-            W = np.concatenate([np.asarray(weights[p + "_w"], np.float32) for p in parts], 0)      # [O, K] (torch layout)
-            b = np.concatenate([np.asarray(weights[p + "_b"], np.float32) for p in parts], 0)
-            O, K = W.shape
-            K8 = (K + 7) & ~7
-            Wt = np.zeros((K8, OP), np.float32)
-            Wt[:K, :O] = W.T
-            buf[d.off[m]:d.off[m] + K8 * OP] = Wt.reshape(K8 // 4, 4, OP).transpose(0, 2, 1).reshape(-1)
-            buf[d.off[15 + m]:d.off[15 + m] + O] = b
-        self.packed = torch.from_numpy(buf).to(self.device)
+        self.packed = torch.from_numpy(pack_mats(weights, d, 8)).to(self.device)
+
+    def single_launch_image(self):
+        return self.wide_desc, self.packed
 
     def recurrent(self, engine):
         x, branch = engine.mlp_input, engine.branch
         B = x.shape[0]
-        hidden, reward = self._out("h", (B, self.S)), self._out("r", (B,))
-        policy, value = self._out("p", (B, self.A)), self._out("v", (B,))
+        hidden, reward, policy, value = self._round_out(B)
         _lib.check(self.lib.smz_mlp_recurrent_wide(C.byref(self.wide_desc), _ptr(self.packed), _ptr(x), _ptr(branch), _ptr(hidden),
                                                    _ptr(reward), _ptr(policy), _ptr(value), B, _stream(self.device)))
         return hidden, reward, policy, value
@@ -309,6 +320,7 @@ class HipMlpLargeHeads(FusedMlpHeads):
     hip_root=True (opt-in): then it is ONE launch on the same packed image (smz_mlp_initial_large; observations of up to 1024
     floats, ValueError above).  Opt-in (Muzero.heads(backend="large")).  Raises ValueError outside the kernel's limits."""
     wants_mlp_input, wants_parent_hidden = False, True
+    single_launch = "large"
 
     def __init__(self, weights, dims, device, hip_root=False):
         super().__init__(weights, dims, device)
@@ -316,12 +328,15 @@ class HipMlpLargeHeads(FusedMlpHeads):
         d = _lib.MlpDesc(int(dims["obs"]), self.A, self.S, self.H, self.L)
         if not hasattr(self.lib, "smz_mlp_layout_large") or self.lib.smz_mlp_layout_large(C.byref(d)) != 0:
             raise ValueError("mlp heads outside the limits of the large-action tile kernel (A <= 1024, H <= 128, 2 S <= 128)")
-        self.large_desc = d     # (not `desc` / `wide_desc`: those mark heads of other single-launch kernels; this one marks smz_search_mlp_large's)
+        self.large_desc = d
         if self.hip_root:
             _check_hip_root(self.lib, self.obs, "smz_mlp_initial_large")
             # (bound on the instance: without the flag `initial` stays FusedMlpHeads.initial itself)
             self.initial = lambda obs: _hip_initial(self, "smz_mlp_initial_large", self.large_desc, obs)
         self.packed = torch.from_numpy(self.pack(weights, d)).to(self.device)
+
+    def single_launch_image(self):
+        return self.large_desc, self.packed
 
     @staticmethod
     def pack(weights, d):
@@ -332,13 +347,11 @@ class HipMlpLargeHeads(FusedMlpHeads):
         buf = np.zeros(d.total_floats, np.float32)
 
         def wide(at, Wt):
-            """Wt [K, O <= OP] input-major -> the 4-way interleaved wide matrix at float offset `at`, K padded to 8."""
-            K, O = Wt.shape
-            P = np.zeros((r8(K), OP), np.float32)
-            P[:K, :O] = Wt
-            buf[at:at + P.size] = P.reshape(r8(K) // 4, 4, OP).transpose(0, 2, 1).reshape(-1)
+            """Wt [K, O <= OP] input-major -> the interleaved wide matrix at float offset `at`, K padded to 8."""
+            img = interleave(Wt, OP, 8)
+            buf[at:at + img.size] = img
 
-        for m, (name, parts) in enumerate(HipMlpHeads._MATS):
+        for m, (name, parts) in enumerate(_MATS):
             if "_mid" in name and d.L == 0:
                 continue
             W = [np.asarray(weights[p + "_w"], np.float32) for p in parts]          # [O, K] each
@@ -370,19 +383,19 @@ class HipMlpLargeHeads(FusedMlpHeads):
         ph, branch = engine.parent_hidden, engine.branch
         B = ph.shape[0]
         assert ph.dtype == torch.float32 and ph.is_contiguous() and ph.shape[1] == self.S
-        hidden, reward = self._out("h", (B, self.S)), self._out("r", (B,))
-        policy, value = self._out("p", (B, self.A)), self._out("v", (B,))
+        hidden, reward, policy, value = self._round_out(B)
         _lib.check(self.lib.smz_mlp_recurrent_large(C.byref(self.large_desc), _ptr(self.packed), _ptr(ph), _ptr(engine.last_action),
                                                     _ptr(branch), _ptr(hidden), _ptr(reward), _ptr(policy), _ptr(value), B,
                                                     _stream(self.device)))
         return hidden, reward, policy, value
 
 
-class HipVisionHeads:
+class HipVisionHeads(Heads):
     """`vision_model` heads (the reference's ResNet-v2 family, compat_vision.py) evaluated by hand-written HIP kernels:
     smz_vision_initial (one workgroup per frame) and smz_vision_recurrent (one wavefront per leaf).  Weights are
     packed once from the five modules into the layout documented at smz_vision_desc (include/smz.h)."""
     wants_mlp_input, wants_parent_hidden = False, True
+    single_launch = "vision"
     is_rgb = True
     records_frames = True       # initial(obs, record=...) appends the frames to the trajectory record in the same launch
     # index constants of include/smz.h
@@ -394,8 +407,7 @@ class HipVisionHeads:
     def __init__(self, representation, prediction, afterstate_prediction, afterstate_dynamics, dynamics, num_actions,
                  support_size, device):
         import numpy as np
-        self.lib = _lib.load()
-        self.device = torch.device(device)
+        super().__init__(device)
         tower = dynamics.sequential_reward[2]
         linears = [m for m in tower if isinstance(m, torch.nn.Linear)]
         self.A, self.Ssup, self.H = int(num_actions), int(support_size), int(linears[0].out_features)
@@ -423,13 +435,8 @@ class HipVisionHeads:
             put(idx, np.concatenate([alpha, (b - mean * alpha).astype(np.float32)]))
 
         def put_linear(idx, lin):
-            W, b = lin.weight.detach().cpu().numpy().astype(np.float32), lin.bias.detach().cpu().numpy().astype(np.float32)
-            O, K = W.shape
-            K4 = (K + 3) & ~3
-            Wt = np.zeros((K4, OP), np.float32)
-            Wt[:K, :O] = W.T
-            put(idx, Wt.reshape(K4 // 4, 4, OP).transpose(0, 2, 1))
-            put(idx + 1, b)
+            put(idx, interleave(lin.weight.detach().cpu().numpy().astype(np.float32).T, OP, 4))
+            put(idx + 1, lin.bias)
 
         def put_tower(idx, seq):
             lins = [m for m in seq if isinstance(m, torch.nn.Linear)]
@@ -466,13 +473,6 @@ class HipVisionHeads:
         put(b + R["WIDEN"], down[3].weight); put_block(b + R["WIDE_A"], b + R["WIDE_B"], b + R["WIDE_BN"], down[4])
         put_block(b + R["LAST_A"], b + R["LAST_B"], b + R["LAST_BN"], representation.sequential_downsampler[1])
         self.weights = torch.from_numpy(buf).to(self.device)
-        self._buf = {}
-
-    def _out(self, name, shape, dtype=torch.float32):
-        t = self._buf.get(name)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = self._buf[name] = torch.empty(*shape, dtype=dtype, device=self.device)
-        return t
 
     def initial(self, obs, record=None):
         """`record` ([B, 3*98*98] or [B,3,98,98] float32, contiguous): the launch also copies the frames there -- the trajectory
@@ -489,8 +489,7 @@ class HipVisionHeads:
     def recurrent(self, engine):
         ph = engine.parent_hidden
         B = ph.shape[0]
-        hidden, reward = self._out("h", (B, 147)), self._out("r", (B,))
-        policy, value = self._out("p", (B, self.A)), self._out("v", (B,))
+        hidden, reward, policy, value = self._round_out(B)         # (S is 147 here: the 3x7x7 hidden state)
         _lib.check(self.lib.smz_vision_recurrent(C.byref(self.desc), _ptr(self.weights), _ptr(ph), ph.stride(0),
                                                  _ptr(engine.last_action), _ptr(engine.branch), _ptr(hidden), _ptr(reward),
                                                  _ptr(policy), _ptr(value), B, _stream(self.device)))
@@ -526,7 +525,7 @@ def lstm_trunks_from_modules(representation, prediction, afterstate_prediction, 
     return trunks, (rep.state_norm.weight.detach().float(), rep.state_norm.bias.detach().float())
 
 
-class LstmTorchHeads:
+class LstmTorchHeads(Heads):
     """`lstm_model` heads (compat_lstm.py) on torch-ROCm ops + the HIP softmax / support-decode epilogues.
 
     The reference calls every head with batch 1: one length-1 sequence from h0 = c0 = 0.  Here every tree is such a
@@ -539,21 +538,13 @@ class LstmTorchHeads:
 
     def __init__(self, representation, prediction, afterstate_prediction, afterstate_dynamics, dynamics, num_actions,
                  support_size, device):
-        self.lib = _lib.load()
-        self.device = torch.device(device)
+        super().__init__(device)
         trunks, rep = lstm_trunks_from_modules(representation, prediction, afterstate_prediction, afterstate_dynamics,
                                                dynamics)
         mv = lambda x: x.to(self.device).contiguous()
         self.trunks = [(mv(w), mv(b), [(mv(wi), mv(bi), mv(bh)) for wi, bi, bh in layers]) for w, b, layers in trunks]
         self.rep = (mv(rep[0]), mv(rep[1]))
         self.A, self.S = int(num_actions), int(support_size)
-        self._buf = {}
-
-    def _out(self, name, shape, dtype=torch.float32):
-        t = self._buf.get(name)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = self._buf[name] = torch.empty(*shape, dtype=dtype, device=self.device)
-        return t
 
     @staticmethod
     def _scale(x):
@@ -596,7 +587,7 @@ class LstmTorchHeads:
         return hidden, reward, policy, value
 
 
-class HipLstmHeads:
+class HipLstmHeads(Heads):
     """`lstm_model` heads evaluated by hand-written HIP kernels (smz_lstm_initial / smz_lstm_recurrent, csrc/smz_lstm.hip):
     the seven recurrent trunks packed once into the LDS layout of smz_lstm_desc (include/smz.h), each trunk's input Linear
     folded into its first LSTM layer on the host (float64 products, rounded once), forget gates and W_hh dropped (zero
@@ -604,12 +595,12 @@ class HipLstmHeads:
     the seven trunks plus four waves of scratch within 160 KB of LDS, which caps S at 48 -- (obs 9, A 4, S 48, L 1) is the last
     shape that fits (159,712 B); (9, 4, 49, 1) needs 175,024 B and (4, 2, 31, 3) 197,616 B."""
     wants_mlp_input, wants_parent_hidden = True, False
+    single_launch = "lstm"
 
     def __init__(self, representation, prediction, afterstate_prediction, afterstate_dynamics, dynamics, num_actions,
                  support_size, device):
         import numpy as np
-        self.lib = _lib.load()
-        self.device = torch.device(device)
+        super().__init__(device)
         trunks, (rep_w, rep_b) = lstm_trunks_from_modules(representation, prediction, afterstate_prediction,
                                                           afterstate_dynamics, dynamics)
         self.A, self.S = int(num_actions), int(support_size)
@@ -626,13 +617,9 @@ class HipLstmHeads:
 
         def put(idx, W, b):
             """W [G, K] (torch layout) -> input-major, 4-way interleaved, row width G; b [G]."""
-            W = np.asarray(W, np.float32)
-            G, K = W.shape
-            K4 = (K + 3) & ~3
-            Wt = np.zeros((K4, G), np.float32)
-            Wt[:K] = W.T
-            buf[d.off[idx]:d.off[idx] + K4 * G] = Wt.reshape(K4 // 4, 4, G).transpose(0, 2, 1).reshape(-1)
-            buf[d.off[idx + 1]:d.off[idx + 1] + G] = np.asarray(b, np.float32)
+            img = interleave(np.asarray(W, np.float32).T, len(b), 4)
+            buf[d.off[idx]:d.off[idx] + img.size] = img
+            buf[d.off[idx + 1]:d.off[idx + 1] + len(b)] = np.asarray(b, np.float32)
 
         f64 = lambda x: x.cpu().double().numpy()
         for t, (w, b, layers) in enumerate(trunks):
@@ -647,13 +634,6 @@ class HipLstmHeads:
                 put(2 * (t * _lib.LstmDesc.MAX_LAYERS + l), W, bias)
         put(_lib.LstmDesc.REP, rep_w.cpu().numpy(), rep_b.cpu().numpy())
         self.weights = torch.from_numpy(buf).to(self.device)
-        self._buf = {}
-
-    def _out(self, name, shape, dtype=torch.float32):
-        t = self._buf.get(name)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = self._buf[name] = torch.empty(*shape, dtype=dtype, device=self.device)
-        return t
 
     def initial(self, obs):
         B = obs.shape[0]
@@ -667,15 +647,14 @@ class HipLstmHeads:
         x, branch = engine.mlp_input, engine.branch
         B = x.shape[0]
         assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == self.S + self.A
-        hidden, reward = self._out("h", (B, self.S)), self._out("r", (B,))
-        policy, value = self._out("p", (B, self.A)), self._out("v", (B,))
+        hidden, reward, policy, value = self._round_out(B)
         _lib.check(self.lib.smz_lstm_recurrent(C.byref(self.desc), _ptr(self.weights), _ptr(x), _ptr(branch),
                                                _ptr(hidden), _ptr(reward), _ptr(policy), _ptr(value), B,
                                                _stream(self.device)))
         return hidden, reward, policy, value
 
 
-class ModuleHeads:
+class ModuleHeads(Heads):
     """Heads given as five torch modules with the reference's signatures:
          representation(obs) -> hidden                                   (already scaled)
          prediction(h), afterstate_prediction(h) -> (policy_logits, value_logits)
@@ -688,18 +667,10 @@ class ModuleHeads:
 
     def __init__(self, representation, prediction, afterstate_prediction, afterstate_dynamics, dynamics, num_actions,
                  support_size, device, is_rgb=False):
-        self.lib = _lib.load()
-        self.device = torch.device(device)
+        super().__init__(device)
         self.rep, self.pre, self.apr, self.ady, self.dyn = (m.to(self.device).eval() for m in (
             representation, prediction, afterstate_prediction, afterstate_dynamics, dynamics))
         self.A, self.Ssup, self.is_rgb = int(num_actions), int(support_size), bool(is_rgb)
-        self._buf = {}
-
-    def _out(self, name, shape, dtype=torch.float32):
-        t = self._buf.get(name)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = self._buf[name] = torch.empty(*shape, dtype=dtype, device=self.device)
-        return t
 
     def encode_action(self, action, hidden):
         if not self.is_rgb:

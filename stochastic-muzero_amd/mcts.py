@@ -8,6 +8,7 @@
                               reference's five `*_inference` methods.  The tree lives on the GPU; the process-global
                               numpy stream is carried in and out so the draws are the reference's draws.
 """
+import collections
 import warnings
 
 import numpy as np
@@ -128,6 +129,22 @@ def resolve_rng_mode(rng_mode, num_trees):
     return int(rng_mode)
 
 
+# The searches that run as ONE launch, by the kind the heads name (heads.Heads.single_launch); "players" is what "mlp" heads get
+# on a multi-player engine (BatchedMCTS._run).  method: the SearchEngine call; flag: the BatchedMCTS attribute that opts
+# in (None: on wherever single launches are); rooted: the kernel takes the outputs of heads.initial (otherwise the observations:
+# it evaluates the root itself); what: the words of its warning when it refuses a geometry (None: search_mlp's own, about LDS).
+SingleLaunch = collections.namedtuple("SingleLaunch", "method flag rooted what")
+SINGLE_LAUNCHES = {
+    "mlp": SingleLaunch("search_mlp", None, False, None),
+    "vision": SingleLaunch("search_vision", None, True, "vision search"),
+    "lstm": SingleLaunch("search_lstm", "lstm_single_launch", True, "lstm search"),
+    "wide": SingleLaunch("search_mlp_wide", "wide_single_launch", True, "wide mlp search"),
+    "large": SingleLaunch("search_mlp_large", "large_single_launch", True, "large-action search"),
+    "players": SingleLaunch("search_mlp_players", "players_single_launch", False, "multi-player search"),
+}
+NO_SINGLE_LAUNCH = SingleLaunch(None, None, False, None)
+
+
 class BatchedMCTS(_Hyper):
     def __init__(self, num_trees, pb_c_base=19652, pb_c_init=1.25, discount=0.95, root_dirichlet_alpha=0.25,
                  root_exploration_fraction=0.25, num_simulations=10, maxium_action_sample=2, number_of_player=1,
@@ -165,7 +182,9 @@ class BatchedMCTS(_Hyper):
         self._graph = None
         self._graph_key = None
         self._graph_heads = None
+        self._static_obs = None
         self._single = None
+        self._active = self._pending_seed = self._recorded = None
         # beyond ~17 k trees the step-wise kernels (64 trees per wavefront, networks as 16-leaf tiles on the matrix cores, rows
         # left in the tree) overtake the single launch: measured on one box (tools/crossover.sh) 440 vs 424 M simulations/s at
         # 16 384 trees, 436 vs 505 at 20 480, 427 vs 586 at 24 576
@@ -178,7 +197,7 @@ class BatchedMCTS(_Hyper):
             self.engine = SearchEngine(self.num_trees, num_actions, hidden_size, device=self.device,
                                        rng_mode=self.rng_mode, large_actions=num_actions > _lib.MAX_ACTIONS,
                                        **self._engine_kwargs())
-            if getattr(self, "_active", None) is not None:
+            if self._active is not None:
                 self.engine.set_active(self._active)
             self._bind_players(self.engine)
             self._graph = None
@@ -194,8 +213,7 @@ class BatchedMCTS(_Hyper):
     def set_active(self, active):
         """uint8 [num_trees] device tensor (or None): trees whose byte is 0 are skipped by run() and act() -- finished
         games stop consuming simulations (self_play.py:79).  A captured graph holds the pointer, so it is dropped."""
-        if active is getattr(self, "_active", None) and (active is None or self.engine is None or
-                                                         getattr(self.engine, "_active", None) is active):
+        if active is self._active and (active is None or self.engine is None or self.engine._active is active):
             return                          # the same array is bound already: a captured graph stays valid
         self._active = active
         self._graph = None
@@ -272,7 +290,7 @@ class BatchedMCTS(_Hyper):
 
     def _seed_pending(self, eng):
         """Hands a seed() given before the engine existed to the engine, once."""
-        if getattr(self, "_pending_seed", None) is not None:
+        if self._pending_seed is not None:
             eng.seed(self._pending_seed)
             self._pending_seed = None
 
@@ -296,58 +314,42 @@ class BatchedMCTS(_Hyper):
         self._recorded = False
         # (single_launch_max_trees: where the step-wise kernels overtake the single launch)
         single = self.single_launch and self._single is not False and self.num_trees <= self.single_launch_max_trees
-        desc = getattr(heads, "desc", None)
+        # the entry of SINGLE_LAUNCHES built for these heads on this engine, if any
+        kind = getattr(heads, "single_launch", None) if single else None
+        if kind is not None:
+            many = int(heads.A) > _lib.MAX_ACTIONS         # more actions than the per-lane kernels take: a large-action handle
+            if self.n_cycle > 1:
+                # the multi-player backup: the launch built for these handles takes the LDS-resident mlp heads; every other
+                # single launch refuses such a handle
+                kind = "players" if kind == "mlp" and not many else None
+            elif (kind == "large") != many:                # the large launch takes a large-action handle, and no other does
+                kind = None
+        method, flag, rooted, what = SINGLE_LAUNCHES.get(kind, NO_SINGLE_LAUNCH)
+        if method is None or not (flag is None or getattr(self, flag)):
+            return self._run_stepwise(observations, heads, train)           # (without a warning: nothing was refused)
+        desc, image = heads.single_launch_image()
         kw = dict(train=train, act_temperature=act_temperature)
-
-        def outside(what):
-            return lambda err: f"single-launch {what} is outside its limits for this configuration ({err}): using the step-wise kernels"
-
-        def rooted(**record):
-            hidden, policy = heads.initial(observations, **record)
-            return hidden, policy, self._ensure_engine(policy.shape[1], hidden.shape[1])
-
-        if self.n_cycle > 1:
-            # the multi-player backup: the step-wise kernels, or (opt-in, HipMlpHeads) the single launch built for these handles;
-            # every other single launch refuses them
-            if single and self.players_single_launch and isinstance(desc, _lib.MlpDesc) and int(heads.A) <= _lib.MAX_ACTIONS:
-                eng = self._ensure_engine(heads.A, heads.S)
-                self._stage_to_play(eng)
-                if self._try_single(eng, lambda: eng.search_mlp_players(heads.desc, heads.weights, observations, **kw),
-                                    outside("multi-player search")):
-                    return eng
-        elif int(getattr(heads, "A", 0)) > _lib.MAX_ACTIONS:
-            # more actions than the per-lane kernels take: the wave-per-tree step-wise kernels, or (opt-in, HipMlpLargeHeads) the
-            # single launch built for these handles; any other heads search step-wise, without a warning
-            if single and self.large_single_launch and isinstance(getattr(heads, "large_desc", None), _lib.MlpDesc):
-                hidden, policy, eng = rooted()
-                if self._try_single(eng, lambda: eng.search_mlp_large(heads.large_desc, heads.packed, hidden, policy, **kw),
-                                    outside("large-action search")):
-                    return eng
-        elif single and isinstance(desc, _lib.MlpDesc):
+        if rooted:
+            # the root evaluation is the heads' own launch (vision: it can record the frames it reads), then the whole search in one
+            record = dict(record=record_obs) if kind == "vision" and record_obs is not None else {}
+            hidden, policy = inputs = heads.initial(observations, **record)
+            self._recorded = bool(record)
+            eng = self._ensure_engine(policy.shape[1], hidden.shape[1])
+        else:
+            inputs = (observations,)
             eng = self._ensure_engine(heads.A, heads.S)
-            if self._try_single(eng, lambda: eng.search_mlp(heads.desc, heads.weights, observations,
-                                                            env_step=env_step if act_temperature is not None else None, **kw),
-                                lambda err: "single-launch search does not fit in LDS for this batch geometry "
-                                            f"({self.num_trees} trees x {self.num_simulations} simulations): using the step-wise kernels"):
-                return eng
-        elif single and isinstance(desc, _lib.VisionDesc):
-            # vision_model heads: representation per frame (its own launch), then the whole search in one launch
-            hidden, policy, eng = rooted(**({} if record_obs is None else dict(record=record_obs)))
-            self._recorded = record_obs is not None
-            if self._try_single(eng, lambda: eng.search_vision(heads.desc, heads.weights, hidden, policy, **kw), outside("vision search")):
-                return eng
-        elif single and self.lstm_single_launch and isinstance(desc, _lib.LstmDesc):
-            # lstm_model heads, opt-in: representation + root policy (its own launch), then the whole search in one launch
-            hidden, policy, eng = rooted()
-            if self._try_single(eng, lambda: eng.search_lstm(heads.desc, heads.weights, hidden, policy, **kw), outside("lstm search")):
-                return eng
-        elif single and self.wide_single_launch and isinstance(getattr(heads, "wide_desc", None), _lib.MlpDesc):
-            # wide mlp_model heads, opt-in: root evaluation (torch GEMMs, or one HIP launch for hip_root heads), then the whole search
-            # in one launch
-            hidden, policy, eng = rooted()
-            if self._try_single(eng, lambda: eng.search_mlp_wide(heads.wide_desc, heads.packed, hidden, policy, **kw),
-                                outside("wide mlp search")):
-                return eng
+        if kind == "players":
+            self._stage_to_play(eng)
+        elif kind == "mlp":
+            kw["env_step"] = env_step if act_temperature is not None else None
+        if what is None:
+            warning = lambda err: ("single-launch search does not fit in LDS for this batch geometry "
+                                   f"({self.num_trees} trees x {self.num_simulations} simulations): using the step-wise kernels")
+        else:
+            warning = lambda err: (f"single-launch {what} is outside its limits for this configuration ({err}): "
+                                   "using the step-wise kernels")
+        if self._try_single(eng, lambda: getattr(eng, method)(desc, image, *inputs, **kw), warning):
+            return eng
         return self._run_stepwise(observations, heads, train)
 
     def _run_stepwise(self, observations, heads, train):

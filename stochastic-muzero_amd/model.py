@@ -296,39 +296,29 @@ class Muzero:
             del self._heads[key]              # the modules were updated in place (optimizer step, load_state_dict, ...)
         self._heads_version[key] = version
         if key not in self._heads:
-            if self.model_structure == "mlp_model" and backend == "large":
-                arrays = mlp_arrays_from_modules(self.representation_function, self.prediction_function,
-                                                 self.afterstate_prediction_function, self.afterstate_dynamics_function,
-                                                 self.dynamics_function)
-                dims = dict(obs=self.observation_dimension, A=self.action_dimension, S=self.state_dimension,
-                            H=self.hidden_layer_dimension, L=self.number_of_hidden_layer)
-                self._heads[key] = HipMlpLargeHeads(arrays, dims, device, hip_root=bool(hip_root))
-                return self._heads[key]
-            if self.model_structure == "mlp_model" and backend in ("auto", "hip"):
-                arrays = mlp_arrays_from_modules(self.representation_function, self.prediction_function,
-                                                 self.afterstate_prediction_function, self.afterstate_dynamics_function,
-                                                 self.dynamics_function)
-                dims = dict(obs=self.observation_dimension, A=self.action_dimension, S=self.state_dimension,
-                            H=self.hidden_layer_dimension, L=self.number_of_hidden_layer)
-                try:
-                    self._heads[key] = HipMlpHeads(arrays, dims, device)
-                    return self._heads[key]
-                except ValueError:
-                    if backend == "hip":
-                        raise
-                try:        # too wide for LDS residency: tiles on the matrix cores with the weights streamed from L2
-                    self._heads[key] = HipMlpTileHeads(arrays, dims, device, hip_root=bool(hip_root))
-                    return self._heads[key]
-                except HipRootLimit:
-                    raise       # (an explicit opt-in does not fall back)
-                except ValueError:
-                    pass
             if self.model_structure == "mlp_model":
                 arrays = mlp_arrays_from_modules(self.representation_function, self.prediction_function,
                                                  self.afterstate_prediction_function, self.afterstate_dynamics_function,
                                                  self.dynamics_function)
                 dims = dict(obs=self.observation_dimension, A=self.action_dimension, S=self.state_dimension,
                             H=self.hidden_layer_dimension, L=self.number_of_hidden_layer)
+                if backend == "large":
+                    self._heads[key] = HipMlpLargeHeads(arrays, dims, device, hip_root=bool(hip_root))
+                    return self._heads[key]
+                if backend in ("auto", "hip"):
+                    try:
+                        self._heads[key] = HipMlpHeads(arrays, dims, device)
+                        return self._heads[key]
+                    except ValueError:
+                        if backend == "hip":
+                            raise
+                    try:        # too wide for LDS residency: tiles on the matrix cores with the weights streamed from L2
+                        self._heads[key] = HipMlpTileHeads(arrays, dims, device, hip_root=bool(hip_root))
+                        return self._heads[key]
+                    except HipRootLimit:
+                        raise       # (an explicit opt-in does not fall back)
+                    except ValueError:
+                        pass
                 assert set(n + s for n in MLP_ARRAYS for s in ("_w", "_b")) <= set(arrays)
                 self._heads[key] = FusedMlpHeads(arrays, dims, device)
             elif self.model_structure == "lstm_model":

@@ -11,13 +11,12 @@ knows one player, so:
     the same tape: the signed backup saw the heads' values.
 The engine's trees at 33 .. 1000 actions and with two players are held to the reference's own fixtures elsewhere
 (tests/test_gpu_large_actions.py, tests/test_gpu_players.py)."""
-from importlib import import_module
-
 import numpy as np
 import pytest
 import torch
 
 import mlp_reference as mr
+from search_helpers import _pkg
 from test_gpu_large_actions import _streams_equal, _trees_equal
 from test_gpu_lstm import _held
 from test_gpu_lstm_envelope import _decoded, _hidden_rows
@@ -25,11 +24,6 @@ from test_gpu_mlp_envelope import TILE_ATOL
 
 pytestmark = pytest.mark.gpu
 GAIN = 4
-
-
-def _pkg(name):
-    import stochastic_muzero_amd  # noqa: F401
-    return import_module("stochastic-muzero_amd." + name)
 
 
 def _obs(B, n, seed):

@@ -11,6 +11,7 @@ import torch
 
 import golden_util as gu
 import lstm_reference as lr
+from search_helpers import _lib, _rng, _same_dumps, _same_states, _snapshot
 from test_gpu_lstm import NETS, _held, _model, _pkg
 from test_records import Buffer, same_game
 
@@ -20,37 +21,8 @@ pytestmark = pytest.mark.gpu
 TPW2 = 2 * 256 * 4 + 1                    # the smallest batch whose wavefronts own two trees
 
 
-def _lib():
-    import stochastic_muzero_amd as smz
-    return smz._lib
-
-
-def _rng(name):
-    return _lib().RNG_PHILOX if name == "philox" else _lib().RNG_MT19937_NUMPY
-
-
 def _obs(model, B, seed=3):
     return (torch.rand(B, model.observation_dimension, generator=torch.Generator().manual_seed(seed)) - 0.5).mul(0.1).cuda().contiguous()
-
-
-def _snapshot(e, B, rng, trees):
-    dumps = [e.dump_tree(i) for i in trees]
-    states = [e.philox_position(i) if rng == "philox" else e.get_rng_state(i) for i in trees]
-    return dumps, states
-
-
-def _same_dumps(da, db):
-    for x, y in zip(da, db):
-        for k in x:
-            assert np.array_equal(np.asarray(x[k]), np.asarray(y[k])), k
-
-
-def _same_states(sa, sb, rng):
-    for x, y in zip(sa, sb):
-        if rng == "philox":
-            assert x == y
-        else:
-            assert np.array_equal(x[0], y[0]) and x[1] == y[1]
 
 
 def _search_pair(model, heads, B, sims, rng, active=None):
@@ -74,7 +46,7 @@ def _search_pair(model, heads, B, sims, rng, active=None):
         visits, priors, rv, cr = e.root_stats()
         torch.cuda.synchronize()
         out = [t.cpu().numpy().copy() for t in (visits, priors, rv, cr, action, policy, cv, rv2)]
-        res.append((out, _snapshot(e, B, rng, sorted({0, B // 2, B - 1})), _snapshot(e, B, rng, sorted({0, B - 1}))[1]))
+        res.append((out, _snapshot(e, rng, sorted({0, B // 2, B - 1})), _snapshot(e, rng, sorted({0, B - 1}))[1]))
     return res
 
 
@@ -147,16 +119,16 @@ def test_masked_trees_are_left_alone(rng):
         m.seed(np.arange(B, dtype=np.uint64) + 4)
         e = m.run(obs, heads, train=True)
         torch.cuda.synchronize()
-        before = _snapshot(e, B, rng, off)
+        before = _snapshot(e, rng, off)
         m.set_active(active)
         e = m.run(obs + 0.01, heads, train=True)
         assert m._single is (True if single else None)
         visits, priors, rv, cr = e.root_stats()
         torch.cuda.synchronize()
-        after = _snapshot(e, B, rng, off)
+        after = _snapshot(e, rng, off)
         _same_dumps(before[0], after[0])
         _same_states(before[1], after[1], rng)
-        res.append(([t.cpu().numpy()[on].copy() for t in (visits, priors, rv, cr)], _snapshot(e, B, rng, on)))
+        res.append(([t.cpu().numpy()[on].copy() for t in (visits, priors, rv, cr)], _snapshot(e, rng, on)))
     for a, b in zip(res[0][0], res[1][0]):
         assert np.array_equal(a, b)
     _same_dumps(res[0][1][0], res[1][1][0])

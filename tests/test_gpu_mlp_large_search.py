@@ -12,13 +12,13 @@ actions), the geometry the ragged workgroups, the switched-off workgroup and T =
 import ctypes as C
 import functools
 import warnings
-from importlib import import_module
 
 import numpy as np
 import pytest
 import torch
 
 import mlp_reference as mr
+from search_helpers import _pkg
 from test_gpu_large_actions import _streams_equal, _trees_equal
 
 pytestmark = pytest.mark.gpu
@@ -34,11 +34,6 @@ def geometry(request, monkeypatch):
     else:
         monkeypatch.delenv("SMZ_LARGE_SEARCH_T", raising=False)
     return request.param
-
-
-def _pkg(name):
-    import stochastic_muzero_amd  # noqa: F401
-    return import_module("stochastic-muzero_amd." + name)
 
 
 @functools.lru_cache(maxsize=None)

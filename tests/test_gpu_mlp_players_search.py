@@ -12,23 +12,13 @@ import torch
 
 import golden_util as gu
 import mlp_reference as mr
+from search_helpers import _lib, _pkg, _states
 
 pytestmark = pytest.mark.gpu
 
 FIELDS = ("visit", "value_sum", "reward", "child_base", "action", "minmax")
 KW = dict(discount=0.999, root_exploration_fraction=0.1)
 CYCLES = {"two": dict(number_of_player=2), "three": dict(number_of_player=3), "loop": dict(custom_loop="1>2>1>3")}
-
-
-def _pkg(name):
-    import stochastic_muzero_amd  # noqa: F401
-    from importlib import import_module
-    return import_module("stochastic-muzero_amd." + name)
-
-
-def _lib():
-    import stochastic_muzero_amd as smz
-    return smz._lib
 
 
 _CACHE = {}
@@ -46,10 +36,6 @@ def _ckpt421():
 
 def _obs(B, dim=4):
     return torch.from_numpy(np.random.RandomState(1).uniform(-0.05, 0.05, (B, dim)).astype(np.float32)).cuda()
-
-
-def _states(e, rng, trees):
-    return [e.philox_position(i) if rng == "philox" else e.get_rng_state(i) for i in trees]
 
 
 def _collect(e, rng, trees, act=True):

@@ -13,6 +13,7 @@ import torch
 
 import golden_util as gu
 import mlp_reference as mr
+from search_helpers import _lib, _pkg, _rng, _same_dumps, _same_states, _snapshot
 from test_records import Buffer, same_game
 
 pytestmark = pytest.mark.gpu
@@ -25,17 +26,6 @@ TPW2 = 1 * 256 * 4 + 1                    # the smallest batch whose wavefronts 
 FRESH = {"s33": (4, 2, 33, 64, 0), "h72": (4, 4, 16, 72, 2)}
 FIXTURES = {"ckpt450": ("weights_ckpt450.npz", "ckpt450_sims11"), "cfg434": ("weights_cfg434shape.npz", "cfg434shape_sims11")}
 NETS = ["s33", "h72", "ckpt450", "cfg434"]
-
-
-def _pkg(name):
-    import stochastic_muzero_amd  # noqa: F401
-    from importlib import import_module
-    return import_module("stochastic-muzero_amd." + name)
-
-
-def _lib():
-    import stochastic_muzero_amd as smz
-    return smz._lib
 
 
 _MODELS = {}
@@ -54,32 +44,8 @@ def _net(name):
     return _MODELS[name]
 
 
-def _rng(name):
-    return _lib().RNG_PHILOX if name == "philox" else _lib().RNG_MT19937_NUMPY
-
-
 def _obs(B, seed=3):
     return (torch.rand(B, 4, generator=torch.Generator().manual_seed(seed)) - 0.5).mul(0.1).cuda().contiguous()
-
-
-def _snapshot(e, rng, trees):
-    dumps = [e.dump_tree(i) for i in trees]
-    states = [e.philox_position(i) if rng == "philox" else e.get_rng_state(i) for i in trees]
-    return dumps, states
-
-
-def _same_dumps(da, db):
-    for x, y in zip(da, db):
-        for k in x:
-            assert np.array_equal(np.asarray(x[k]), np.asarray(y[k])), k
-
-
-def _same_states(sa, sb, rng):
-    for x, y in zip(sa, sb):
-        if rng == "philox":
-            assert x == y
-        else:
-            assert np.array_equal(x[0], y[0]) and x[1] == y[1]
 
 
 def _search_pair(heads, B, sims, rng, K=2):

@@ -173,6 +173,53 @@ def test_packing_round_trip():
     assert 0 < seen.sum() < img.size and (img[~seen] == 0).all()
 
 
+# (layout entry point, name of the evaluator, its image, its descriptor, (obs, A, S, H, L), OP, K is padded to a multiple of):
+# odd sizes that are no multiple of the padding, with hidden layers; the wide shape is one the LDS layout refuses (2 S > 64)
+PLAIN_IMAGES = [("smz_mlp_layout", "HipMlpHeads", "weights", "desc", (5, 3, 5, 7, 2), 64, 4),
+                ("smz_mlp_layout_wide", "HipMlpTileHeads", "packed", "wide_desc", (5, 3, 33, 70, 2), 128, 8)]
+
+
+@pytest.mark.parametrize("entry,cls,image,desc,shape,op,pad", PLAIN_IMAGES, ids=[p[0] for p in PLAIN_IMAGES])
+def test_lds_and_wide_packing_round_trip(entry, cls, image, desc, shape, op, pad):
+    """The other two mlp_model images, as the evaluators built on the CPU device hold them, of a fresh net each: every weight at
+    off[m] + ((k / 4) * OP + o) * 4 + k % 4 and every bias at off[15 + m] + o (include/smz.h) against mlp_arrays_from_modules,
+    matrix by matrix in the documented order; K padded to 4 (LDS) or 8 (wide) inputs; everything else in the image exactly 0."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import mlp_reference as mr
+    heads_mod, model_mod = _pkg("heads"), _pkg("model")
+    model = mr.fresh_net(*shape, seed=7, gain=4)
+    w = {k: np.asarray(v) for k, v in model_mod.mlp_arrays_from_modules(
+        model.representation_function, model.prediction_function, model.afterstate_prediction_function,
+        model.afterstate_dynamics_function, model.dynamics_function).items()}
+    obs, A, S, H, L = shape
+    heads = getattr(heads_mod, cls)(w, dict(obs=obs, A=A, S=S, H=H, L=L), "cpu")
+    d, img = getattr(heads, desc), getattr(heads, image).numpy()
+    assert d.OP == op and img.dtype == np.float32 and img.size == d.total_floats
+    seen = np.zeros(img.size, bool)
+    mats = [["dyn_in"], ["ady_in"], ["dyn_mid"], ["ady_mid"], ["dyn_rw", "dyn_st"], ["ady_st"], ["pre_in"], ["apr_in"], ["pre_mid"],
+            ["apr_mid"], ["pre_pol", "pre_val"], ["apr_pol", "apr_val"], ["rep_in"], ["rep_mid"], ["rep_out"]]
+    shapes = [(S + A, H), (S + A, H), (H, H), (H, H), (H, 2 * S), (H, S), (S, H), (S, H), (H, H), (H, H), (H, A + S), (H, A + S),
+              (obs, H), (H, H), (H, S)]
+    for m, parts in enumerate(mats):
+        Wt = np.concatenate([w[p + "_w"] for p in parts], 0).T            # [K, O]
+        b = np.concatenate([w[p + "_b"] for p in parts], 0)
+        K, O = Wt.shape
+        assert (K, O) == shapes[m] and b.shape == (O,) and O <= op
+        for k in range(K):
+            for o in range(O):
+                i = d.off[m] + ((k // 4) * op + o) * 4 + k % 4
+                assert img[i] == Wt[k, o] and not seen[i], (m, k, o)
+                seen[i] = True
+        for o in range(O):
+            i = d.off[15 + m] + o
+            assert img[i] == b[o] and not seen[i], (m, o)
+            seen[i] = True
+        # the matrix's padded rows end where the next piece begins, or before
+        nxt = min([x for x in list(d.off) + [d.total_floats] if x > d.off[m]])
+        assert d.off[m] + (K + pad - 1) // pad * pad * op <= nxt, m
+    assert 0 < seen.sum() < img.size and (img[~seen] == 0).all()
+
+
 def test_the_image_read_with_the_kernels_addresses_gives_the_restatements_outputs():
     """The packed image of a fresh (4,129,5,7,2) net evaluated in float64 numpy through the address arithmetic of
     csrc/smz_mlp_large.hip -- hidden part + action-table row, 8-input groups, panels, one bias vector per panel -- on 64 rows

@@ -546,7 +546,41 @@ int smz_mlp_recurrent_large(const smz_mlp_desc *desc, const float *weights_dev, 
                             const int32_t *last_action_dev, const uint8_t *branch_dev, float *hidden_out_dev,
                             float *reward_out_dev, float *policy_out_dev, float *value_out_dev, int B, smz_stream stream);
 
-/* The ROOT evaluation of those two families in one launch each (csrc/smz_mlp_root.hip): smz_mlp_initial on an image of
+/* The recurrent mlp_model networks up to 512 wide: 1 <= H <= 512, 1 <= S <= 256, 1 <= A <= SMZ_MAX_ACTIONS_LARGE, obs >= 1,
+ * L >= 0 (SMZ_ERR_TOO_LARGE above those limits; SMZ_ERR_INVALID for a null descriptor, a non-positive dimension or L < 0).
+ * smz_mlp_layout_broad fills the same descriptor (OP = 128) for a packed image in which EVERY matrix is a sequence of
+ * 128-column panels.  R8(x) = x rounded up to a multiple of 8, P(n) = ceil(n / 128).  A "panel matrix" of K inputs and O
+ * outputs at base, with its biases at bias, is P(O) panels of R8(K) x 128 floats each, panel p holding output columns
+ * 128 p .. min(O, 128 p + 128) - 1 as a wide matrix (input-major, 4-way interleaved, K padded to R8(K), rows 128 wide):
+ *     weight (k, o)  at  base + (o / 128) * R8(K) * 128 + ((k / 4) * 128 + o % 128) * 4 + k % 4
+ *     bias o         at  bias + o                      (P(O) vectors of 128 floats, one per panel)
+ * and everything else in it is zero.  Matrices (off[] index m; biases at off[15 + m]):
+ *   0 dyn_in, 1 ady_in       the hidden part, a panel matrix of K = S, O = H (inputs 0 .. S - 1 of the torch weight), then the
+ *                            action table [A][128 P(H)]: element (a, o) at off[m] + P(H) * R8(S) * 128 + a * 128 * P(H) + o
+ *                            = weight of input S + a for neuron o.  Biases: P(H) vectors.
+ *   2 dyn_mid, 3 ady_mid, 8 pre_mid, 9 apr_mid, 13 rep_mid      panel matrices of K = H, O = H; nothing at all when L = 0
+ *   4 dyn_out                TWO panel matrices of K = H, O = S one behind the other, each column range in panels of its own:
+ *                            the reward logits (torch outputs 0 .. S - 1) at off[4], biases at off[19]; the next state
+ *                            (torch outputs S .. 2 S - 1) at off[4] + P(S) * R8(H) * 128, biases at off[19] + 128 P(S)
+ *   5 ady_out, 14 rep_out    panel matrices of K = H, O = S
+ *   6 pre_in, 7 apr_in       panel matrices of K = S, O = H;   12 rep_in: K = obs, O = H
+ *   10 pre_out, 11 apr_out   the policy, a panel matrix of K = H, O = A, at off[m], biases at off[15 + m]; then the value, a
+ *                            panel matrix of K = H, O = S, at off[m] + P(A) * R8(H) * 128, biases at off[15 + m] + 128 P(A)
+ * The pieces follow one another without gaps: the 15 matrices in index order, then the 15 bias pieces in index order.  The
+ * representation matrices are packed in the same form; smz_mlp_recurrent_broad does not read them.
+ * smz_mlp_recurrent_broad: smz_mlp_recurrent_large's arguments, rows and outputs on such an image, one launch (16-leaf tiles
+ * on the matrix cores, a workgroup of four wavefronts per tile sharing every layer's panels, weights streamed from L2; the
+ * reductions between the layers and the softmax run across the panels).  A last_action outside [0, A) is evaluated as action
+ * 0 and never becomes an address; a row's outputs do not depend on the batch it is evaluated in; reward_out is 0 on afterstate
+ * rows.  No allocation, no host read: safe under stream capture.  SMZ_ERR_INVALID, with nothing launched: a null pointer,
+ * B < 1, a descriptor smz_mlp_layout_broad would not produce (one of smz_mlp_layout_wide or _large included).
+ * neural_network_mlp_model.py:5-250, muzero_model.py:844-909. */
+int smz_mlp_layout_broad(smz_mlp_desc *desc);
+int smz_mlp_recurrent_broad(const smz_mlp_desc *desc, const float *weights_dev, const float *parent_hidden_dev,
+                            const int32_t *last_action_dev, const uint8_t *branch_dev, float *hidden_out_dev,
+                            float *reward_out_dev, float *policy_out_dev, float *value_out_dev, int B, smz_stream stream);
+
+/* The ROOT evaluation of the wide and the large-action families in one launch each (csrc/smz_mlp_root.hip): smz_mlp_initial on an image of
  * smz_mlp_layout_wide (smz_mlp_initial_wide) or of smz_mlp_layout_large (smz_mlp_initial_large) -- representation +
  * scale_to_bound_action + root prediction trunk + policy softmax: obs_dev [B,obs] -> hidden_out_dev [B,S] (scaled),
  * policy_out_dev [B,A] (softmax; while smz_mlp_initial_large runs it also parks the logits there).  They read the rep_in /

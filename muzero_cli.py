@@ -66,9 +66,15 @@ def set_heads_backend(model, config):
     argument of BatchedMCTS: mcts_kwargs leaves it out) makes model.heads(device) hand out the large-action HIP heads
     (Muzero.heads_backend = "large"); a config without the key leaves the model alone.
     "hip_root_evaluation": true in the same section (the same kind of key) makes the wide and the large-action HIP heads evaluate
-    the root in one HIP launch as well (Muzero.hip_root = True); every other evaluator ignores it."""
+    the root in one HIP launch as well (Muzero.hip_root = True); every other evaluator ignores it.
+    "broad_heads": true in the same section (the same kind of key) hands out the HIP heads for networks up to 512 wide
+    (Muzero.heads_backend = "broad"); together with "large_action_heads" it is a ValueError: a model has one backend."""
+    if config["monte_carlo_tree_search"].get("large_action_heads") and config["monte_carlo_tree_search"].get("broad_heads"):
+        raise ValueError('"large_action_heads" and "broad_heads" are both true: choose one heads backend')
     if config["monte_carlo_tree_search"].get("large_action_heads"):
         model.heads_backend = "large"
+    if config["monte_carlo_tree_search"].get("broad_heads"):
+        model.heads_backend = "broad"
     if config["monte_carlo_tree_search"].get("hip_root_evaluation"):
         model.hip_root = True
     return model

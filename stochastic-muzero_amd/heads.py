@@ -390,6 +390,72 @@ class HipMlpLargeHeads(FusedMlpHeads):
         return hidden, reward, policy, value
 
 
+class HipMlpBroadHeads(FusedMlpHeads):
+    """`mlp_model` heads up to 512 wide (hidden_layer_dimensions <= 512, state_space_dimensions <= 256, up to 1024 actions):
+    the recurrent networks as ONE hand-written kernel per simulation round (smz_mlp_recurrent_broad, csrc/smz_mlp_broad.hip)
+    on the parent's hidden row and the action itself.  Every layer of the packed image (smz_mlp_layout_broad, include/smz.h)
+    is a sequence of 128-column panels; the input matrices are a hidden part + an action table.  The root evaluation is
+    FusedMlpHeads.initial, on the torch GEMMs (once per search); no single-launch search takes these heads.  Opt-in
+    (Muzero.heads(backend="broad")).  Raises ValueError outside the kernel's limits."""
+    wants_mlp_input, wants_parent_hidden = False, True
+    single_launch = None
+
+    def __init__(self, weights, dims, device):
+        super().__init__(weights, dims, device)
+        d = _lib.MlpDesc(int(dims["obs"]), self.A, self.S, self.H, self.L)
+        if not hasattr(self.lib, "smz_mlp_layout_broad") or self.lib.smz_mlp_layout_broad(C.byref(d)) != 0:
+            raise ValueError("mlp heads outside the limits of the broad tile kernel (H <= 512, S <= 256, A <= 1024)")
+        self.broad_desc = d
+        self.packed = torch.from_numpy(self.pack(weights, d)).to(self.device)
+
+    @staticmethod
+    def pack(weights, d):
+        """The float32 image smz_mlp_layout_broad describes, from the torch-layout arrays ([O, K] weights)."""
+        import numpy as np
+        A, S, H, OP = d.A, d.S, d.H, d.OP
+        r8 = lambda k: (k + 7) & ~7
+        P = lambda n: (n + OP - 1) // OP
+        buf = np.zeros(d.total_floats, np.float32)
+
+        def panels(at, bias, W, b):
+            """W [O, K], b [O] -> P(O) panels of r8(K) x OP floats at `at`, one bias vector of OP floats per panel at `bias`;
+            returns the float offsets behind them."""
+            O, K = W.shape
+            for p in range(P(O)):
+                lo, hi = p * OP, min(O, (p + 1) * OP)
+                img = interleave(W[lo:hi].T, OP, 8)
+                buf[at:at + img.size] = img
+                buf[bias:bias + hi - lo] = b[lo:hi]
+                at, bias = at + r8(K) * OP, bias + OP
+            return at, bias
+
+        for m, (name, parts) in enumerate(_MATS):
+            if "_mid" in name and d.L == 0:
+                continue
+            W = [np.asarray(weights[p + "_w"], np.float32) for p in parts]          # [O, K] each
+            b = [np.asarray(weights[p + "_b"], np.float32) for p in parts]
+            at, bias = d.off[m], d.off[15 + m]
+            if name in ("dyn_in", "ady_in"):            # hidden part, then the action table [A][OP * P(H)]
+                at, _ = panels(at, bias, W[0][:, :S], b[0])
+                table = np.zeros((A, OP * P(H)), np.float32)
+                table[:, :H] = W[0][:, S:].T
+                buf[at:at + table.size] = table.reshape(-1)
+            else:                                       # each part in panels of its own: reward | state, policy | value
+                for Wp, bp in zip(W, b):
+                    at, bias = panels(at, bias, Wp, bp)
+        return buf
+
+    def recurrent(self, engine):
+        ph, branch = engine.parent_hidden, engine.branch
+        B = ph.shape[0]
+        assert ph.dtype == torch.float32 and ph.is_contiguous() and ph.shape[1] == self.S
+        hidden, reward, policy, value = self._round_out(B)
+        _lib.check(self.lib.smz_mlp_recurrent_broad(C.byref(self.broad_desc), _ptr(self.packed), _ptr(ph), _ptr(engine.last_action),
+                                                    _ptr(branch), _ptr(hidden), _ptr(reward), _ptr(policy), _ptr(value), B,
+                                                    _stream(self.device)))
+        return hidden, reward, policy, value
+
+
 class HipVisionHeads(Heads):
     """`vision_model` heads (the reference's ResNet-v2 family, compat_vision.py) evaluated by hand-written HIP kernels:
     smz_vision_initial (one workgroup per frame) and smz_vision_recurrent (one wavefront per leaf).  Weights are

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import compat_lstm, compat_mlp, compat_vision
-from .heads import (MLP_ARRAYS, FusedMlpHeads, HipLstmHeads, HipMlpHeads, HipMlpLargeHeads, HipMlpTileHeads, HipRootLimit, HipVisionHeads, LstmTorchHeads,
+from .heads import (MLP_ARRAYS, FusedMlpHeads, HipLstmHeads, HipMlpBroadHeads, HipMlpHeads, HipMlpLargeHeads, HipMlpTileHeads, HipRootLimit, HipVisionHeads, LstmTorchHeads,
                     ModuleHeads)
 
 _FUNCS = ("representation", "prediction", "afterstate_prediction", "afterstate_dynamics", "dynamics", "encoder")
@@ -282,6 +282,8 @@ class Muzero:
         the networks fit a CU's LDS; vision_model), "torch" = torch-ROCm GEMMs + HIP epilogues, "auto" = hip when possible,
         else (mlp_model) the wide tile kernel for the recurrent networks when the shape is within its limits, else torch;
         "large" (mlp_model, opt-in) = the large-action tile kernel, up to 1024 actions (ValueError outside its limits);
+        "broad" (mlp_model, opt-in) = the panel tile kernel for the recurrent networks, hidden_layer_dimensions up to 512 and
+        state_space_dimensions up to 256 (ValueError outside its limits; the root stays on the torch GEMMs);
         None = self.heads_backend ("auto" unless set).
         hip_root (opt-in; None = self.hip_root, False unless set): the wide and the large tile heads evaluate the root in ONE
         HIP launch too (smz_mlp_initial_wide / _large) instead of the torch GEMMs; every other evaluator ignores it.
@@ -304,6 +306,9 @@ class Muzero:
                             H=self.hidden_layer_dimension, L=self.number_of_hidden_layer)
                 if backend == "large":
                     self._heads[key] = HipMlpLargeHeads(arrays, dims, device, hip_root=bool(hip_root))
+                    return self._heads[key]
+                if backend == "broad":
+                    self._heads[key] = HipMlpBroadHeads(arrays, dims, device)
                     return self._heads[key]
                 if backend in ("auto", "hip"):
                     try:

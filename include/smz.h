@@ -580,6 +580,48 @@ int smz_mlp_recurrent_broad(const smz_mlp_desc *desc, const float *weights_dev, 
                             const int32_t *last_action_dev, const uint8_t *branch_dev, float *hidden_out_dev,
                             float *reward_out_dev, float *policy_out_dev, float *value_out_dev, int B, smz_stream stream);
 
+/* The same networks over the same envelope (1 <= H <= 512, 1 <= S <= 256, 1 <= A <= SMZ_MAX_ACTIONS_LARGE, obs >= 1, L >= 0; the
+ * same SMZ_ERR_TOO_LARGE / SMZ_ERR_INVALID) with bf16 operands on the matrix cores (csrc/smz_mlp_broad_bf16.hip).
+ * THE ARITHMETIC, a contract of its own (it is NOT torch.autocast's, and not the float32 kernels'):
+ *   - every weight, the rows of the two action tables included, is rounded to bf16, round-to-nearest-even, ONCE, when the image
+ *     is packed on the host (a one-hot input times a bf16 weight is that weight); biases stay float32;
+ *   - the input of every Linear layer is rounded to bf16 (nearest even) where it is written into the LDS activation tile: the
+ *     parent's hidden row, every ELU(...) output, the scaled next state that feeds the prediction network;
+ *   - everything else is float32, in the order of the float32 broad kernel: accumulation in the MFMA (from the bias, in input
+ *     order), the action-table row added to the sums, ELU, minimum / maximum / span (span < 1e-5 -> + 1e-5), the softmax, both
+ *     support decodes, reductions across panels combined in panel order;
+ *   - hidden_out receives the UNROUNDED float32 scaled state: the tree keeps float32 rows, the next round rounds them on load.
+ * smz_mlp_layout_broad_bf16 fills the descriptor (OP = 128) for an image of total_floats 4-BYTE WORDS; off[] counts words.
+ * Biases are float32 words; every other piece is bf16, element e of a piece at word w in bits 16 (e % 2) .. 16 (e % 2) + 15 of
+ * word w + e / 2.  R32(x) = x rounded up to a multiple of 32, P(n) = ceil(n / 128).  A "panel matrix" of K inputs and O outputs
+ * at word base, biases at word bias, is P(O) panels of R32(K) x 128 bf16 (R32(K) * 64 words) each, panel p holding output
+ * columns 128 p .. min(O, 128 p + 128) - 1: per 32-input step, per 16-output tile, the 64 operand fragments of 8 bf16 of
+ * v_mfma_f32_16x16x32_bf16 (lane l: output l % 16, inputs 8 (l / 16) .. 8 (l / 16) + 7):
+ *     weight (k, o)  at bf16 element  (o / 128) * R32(K) * 128 + (k / 32) * 4096 + (o % 128 / 16) * 512
+ *                                     + ((k % 32 / 8) * 16 + o % 16) * 8 + k % 8          of the piece at base
+ *     bias o         at word  bias + o                              (P(O) vectors of 128 floats, one per panel)
+ * and every other element (padding inputs, padding outputs, padding biases) is zero.  Matrices (off[] index m; biases at
+ * off[15 + m]) are those of smz_mlp_layout_broad:
+ *   0 dyn_in, 1 ady_in       the hidden part, a panel matrix of K = S, O = H, then the action table [A][128 P(H)] bf16 at word
+ *                            off[m] + P(H) * R32(S) * 64: element (a, o) at bf16 element a * 128 * P(H) + o of the table
+ *                            = weight of input S + a for neuron o.  Biases: P(H) vectors.
+ *   2 dyn_mid, 3 ady_mid, 8 pre_mid, 9 apr_mid, 13 rep_mid      panel matrices of K = H, O = H; nothing at all when L = 0
+ *   4 dyn_out                the reward logits at off[4], biases at off[19]; the next state at off[4] + P(S) * R32(H) * 64,
+ *                            biases at off[19] + 128 P(S)
+ *   5 ady_out, 14 rep_out    panel matrices of K = H, O = S
+ *   6 pre_in, 7 apr_in       panel matrices of K = S, O = H;   12 rep_in: K = obs, O = H
+ *   10 pre_out, 11 apr_out   the policy at off[m], biases at off[15 + m]; then the value at off[m] + P(A) * R32(H) * 64, biases
+ *                            at off[15 + m] + 128 P(A)
+ * The pieces follow one another without gaps: the 15 matrices in index order, then the 15 bias pieces.  The representation
+ * matrices are packed in the same form and unused.
+ * smz_mlp_recurrent_broad_bf16: smz_mlp_recurrent_broad's arguments, rows, outputs and promises on such an image (weights_dev:
+ * the image).  SMZ_ERR_INVALID, with nothing launched: a null pointer, B < 1, a descriptor smz_mlp_layout_broad_bf16 would
+ * not produce (one of smz_mlp_layout_wide, _large or _broad included). */
+int smz_mlp_layout_broad_bf16(smz_mlp_desc *desc);
+int smz_mlp_recurrent_broad_bf16(const smz_mlp_desc *desc, const void *weights_dev, const float *parent_hidden_dev,
+                                 const int32_t *last_action_dev, const uint8_t *branch_dev, float *hidden_out_dev,
+                                 float *reward_out_dev, float *policy_out_dev, float *value_out_dev, int B, smz_stream stream);
+
 /* The ROOT evaluation of the wide and the large-action families in one launch each (csrc/smz_mlp_root.hip): smz_mlp_initial on an image of
  * smz_mlp_layout_wide (smz_mlp_initial_wide) or of smz_mlp_layout_large (smz_mlp_initial_large) -- representation +
  * scale_to_bound_action + root prediction trunk + policy softmax: obs_dev [B,obs] -> hidden_out_dev [B,S] (scaled),

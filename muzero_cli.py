@@ -68,13 +68,15 @@ def set_heads_backend(model, config):
     "hip_root_evaluation": true in the same section (the same kind of key) makes the wide and the large-action HIP heads evaluate
     the root in one HIP launch as well (Muzero.hip_root = True); every other evaluator ignores it.
     "broad_heads": true in the same section (the same kind of key) hands out the HIP heads for networks up to 512 wide
-    (Muzero.heads_backend = "broad"); together with "large_action_heads" it is a ValueError: a model has one backend."""
-    if config["monte_carlo_tree_search"].get("large_action_heads") and config["monte_carlo_tree_search"].get("broad_heads"):
-        raise ValueError('"large_action_heads" and "broad_heads" are both true: choose one heads backend')
-    if config["monte_carlo_tree_search"].get("large_action_heads"):
-        model.heads_backend = "large"
-    if config["monte_carlo_tree_search"].get("broad_heads"):
-        model.heads_backend = "broad"
+    (Muzero.heads_backend = "broad"); "broad_bf16_heads": true hands out the same family with bf16 operands on the matrix
+    cores (Muzero.heads_backend = "broad_bf16": its own arithmetic, include/smz.h).  Two of "large_action_heads", "broad_heads"
+    and "broad_bf16_heads" together are a ValueError: a model has one backend."""
+    keys = {"large_action_heads": "large", "broad_heads": "broad", "broad_bf16_heads": "broad_bf16"}
+    chosen = [k for k in keys if config["monte_carlo_tree_search"].get(k)]
+    if len(chosen) > 1:
+        raise ValueError(" and ".join(f'"{k}"' for k in chosen) + " are all true: choose one heads backend")
+    if chosen:
+        model.heads_backend = keys[chosen[0]]
     if config["monte_carlo_tree_search"].get("hip_root_evaluation"):
         model.hip_root = True
     return model

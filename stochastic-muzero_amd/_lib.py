@@ -104,6 +104,8 @@ SIGNATURES = {
     "smz_mlp_recurrent_large": (C.c_int, [C.POINTER(MlpDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "smz_mlp_layout_broad": (C.c_int, [C.POINTER(MlpDesc)]),
     "smz_mlp_recurrent_broad": (C.c_int, [C.POINTER(MlpDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
+    "smz_mlp_layout_broad_bf16": (C.c_int, [C.POINTER(MlpDesc)]),
+    "smz_mlp_recurrent_broad_bf16": (C.c_int, [C.POINTER(MlpDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "smz_mlp_initial_wide": (C.c_int, [C.POINTER(MlpDesc), _P, _P, _P, _P, C.c_int, _P]),
     "smz_mlp_initial_large": (C.c_int, [C.POINTER(MlpDesc), _P, _P, _P, _P, C.c_int, _P]),
     "smz_lstm_layout": (C.c_int, [C.POINTER(LstmDesc)]),

@@ -456,6 +456,87 @@ class HipMlpBroadHeads(FusedMlpHeads):
         return hidden, reward, policy, value
 
 
+class HipMlpBroadBf16Heads(FusedMlpHeads):
+    """HipMlpBroadHeads' envelope (hidden_layer_dimensions <= 512, state_space_dimensions <= 256, up to 1024 actions) with bf16
+    operands on the matrix cores: ONE launch of smz_mlp_recurrent_broad_bf16 (csrc/smz_mlp_broad_bf16.hip) per simulation round.
+    The arithmetic is the contract of include/smz.h, not torch.autocast's: weights rounded to bf16 (nearest even) once, here in
+    pack(); every Linear input rounded to bf16 in the kernel; biases, accumulation, ELU, scaling, softmax and support decodes in
+    float32; the hidden rows handed back to the tree are unrounded float32.  The root evaluation is FusedMlpHeads.initial, in
+    float32 on the torch GEMMs (once per search); no single-launch search takes these heads.  Opt-in
+    (Muzero.heads(backend="broad_bf16")).  Raises ValueError outside the kernel's limits."""
+    wants_mlp_input, wants_parent_hidden = False, True
+    single_launch = None
+
+    def __init__(self, weights, dims, device):
+        super().__init__(weights, dims, device)
+        d = _lib.MlpDesc(int(dims["obs"]), self.A, self.S, self.H, self.L)
+        if not hasattr(self.lib, "smz_mlp_layout_broad_bf16") or self.lib.smz_mlp_layout_broad_bf16(C.byref(d)) != 0:
+            raise ValueError("mlp heads outside the limits of the bf16 broad tile kernel (H <= 512, S <= 256, A <= 1024)")
+        self.broad_bf16_desc = d
+        self.packed = torch.from_numpy(self.pack(weights, d).view("int32")).to(self.device)
+
+    @staticmethod
+    def round_bf16(x):
+        """float32 array -> uint16 array of bf16 bit patterns, round-to-nearest-even (NaN stays NaN)."""
+        import numpy as np
+        u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+        r = ((u + (np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1)))) >> np.uint32(16)).astype(np.uint16)
+        nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+        return np.where(nan, ((u >> np.uint32(16)) | np.uint32(0x40)).astype(np.uint16), r)
+
+    @staticmethod
+    def pack(weights, d):
+        """The image smz_mlp_layout_broad_bf16 describes as uint32 words, from the torch-layout arrays ([O, K] weights): float32
+        bit patterns for the biases, pairs of bf16 (low half first) everywhere else."""
+        import numpy as np
+        A, S, H, OP = d.A, d.S, d.H, d.OP
+        r32 = lambda k: (k + 31) & ~31
+        P = lambda n: (n + OP - 1) // OP
+        words = np.zeros(d.total_floats, np.uint32)
+        halves, floats = words.view(np.uint16), words.view(np.float32)      # (little endian: element e of word w at 2 w + e)
+
+        def panels(at, bias, W, b):
+            """W [O, K], b [O] -> P(O) panels of r32(K) x OP bf16 at word `at`, one bias vector of OP floats per panel at word
+            `bias`; returns the word offsets behind them."""
+            O, K = W.shape
+            for p in range(P(O)):
+                lo, hi = p * OP, min(O, (p + 1) * OP)
+                full = np.zeros((r32(K), OP), np.float32)                   # [k][o]
+                full[:K, :hi - lo] = W[lo:hi].T
+                # [step][k % 32 / 8][k % 8][tile][o % 16] -> [step][tile][k % 32 / 8][o % 16][k % 8]
+                img = full.reshape(r32(K) // 32, 4, 8, OP // 16, 16).transpose(0, 3, 1, 4, 2)
+                halves[2 * at:2 * at + img.size] = HipMlpBroadBf16Heads.round_bf16(img.reshape(-1))
+                floats[bias:bias + hi - lo] = b[lo:hi]
+                at, bias = at + r32(K) * OP // 2, bias + OP
+            return at, bias
+
+        for m, (name, parts) in enumerate(_MATS):
+            if "_mid" in name and d.L == 0:
+                continue
+            W = [np.asarray(weights[p + "_w"], np.float32) for p in parts]          # [O, K] each
+            b = [np.asarray(weights[p + "_b"], np.float32) for p in parts]
+            at, bias = d.off[m], d.off[15 + m]
+            if name in ("dyn_in", "ady_in"):            # hidden part, then the action table [A][OP * P(H)] bf16
+                at, _ = panels(at, bias, W[0][:, :S], b[0])
+                table = np.zeros((A, OP * P(H)), np.float32)
+                table[:, :H] = W[0][:, S:].T
+                halves[2 * at:2 * at + table.size] = HipMlpBroadBf16Heads.round_bf16(table.reshape(-1))
+            else:                                       # each part in panels of its own: reward | state, policy | value
+                for Wp, bp in zip(W, b):
+                    at, bias = panels(at, bias, Wp, bp)
+        return words
+
+    def recurrent(self, engine):
+        ph, branch = engine.parent_hidden, engine.branch
+        B = ph.shape[0]
+        assert ph.dtype == torch.float32 and ph.is_contiguous() and ph.shape[1] == self.S
+        hidden, reward, policy, value = self._round_out(B)
+        _lib.check(self.lib.smz_mlp_recurrent_broad_bf16(C.byref(self.broad_bf16_desc), _ptr(self.packed), _ptr(ph),
+                                                         _ptr(engine.last_action), _ptr(branch), _ptr(hidden), _ptr(reward),
+                                                         _ptr(policy), _ptr(value), B, _stream(self.device)))
+        return hidden, reward, policy, value
+
+
 class HipVisionHeads(Heads):
     """`vision_model` heads (the reference's ResNet-v2 family, compat_vision.py) evaluated by hand-written HIP kernels:
     smz_vision_initial (one workgroup per frame) and smz_vision_recurrent (one wavefront per leaf).  Weights are

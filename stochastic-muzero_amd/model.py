@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import compat_lstm, compat_mlp, compat_vision
-from .heads import (MLP_ARRAYS, FusedMlpHeads, HipLstmHeads, HipMlpBroadHeads, HipMlpHeads, HipMlpLargeHeads, HipMlpTileHeads, HipRootLimit, HipVisionHeads, LstmTorchHeads,
+from .heads import (MLP_ARRAYS, FusedMlpHeads, HipLstmHeads, HipMlpBroadBf16Heads, HipMlpBroadHeads, HipMlpHeads, HipMlpLargeHeads, HipMlpTileHeads, HipRootLimit, HipVisionHeads, LstmTorchHeads,
                     ModuleHeads)
 
 _FUNCS = ("representation", "prediction", "afterstate_prediction", "afterstate_dynamics", "dynamics", "encoder")
@@ -284,6 +284,9 @@ class Muzero:
         "large" (mlp_model, opt-in) = the large-action tile kernel, up to 1024 actions (ValueError outside its limits);
         "broad" (mlp_model, opt-in) = the panel tile kernel for the recurrent networks, hidden_layer_dimensions up to 512 and
         state_space_dimensions up to 256 (ValueError outside its limits; the root stays on the torch GEMMs);
+        "broad_bf16" (mlp_model, opt-in) = the same family and limits with bf16 operands on the matrix cores: bf16 weights, every
+        Linear input rounded to bf16, float32 elsewhere -- the arithmetic stated in include/smz.h, not torch.autocast's (the root
+        stays in float32 on the torch GEMMs);
         None = self.heads_backend ("auto" unless set).
         hip_root (opt-in; None = self.hip_root, False unless set): the wide and the large tile heads evaluate the root in ONE
         HIP launch too (smz_mlp_initial_wide / _large) instead of the torch GEMMs; every other evaluator ignores it.
@@ -309,6 +312,9 @@ class Muzero:
                     return self._heads[key]
                 if backend == "broad":
                     self._heads[key] = HipMlpBroadHeads(arrays, dims, device)
+                    return self._heads[key]
+                if backend == "broad_bf16":
+                    self._heads[key] = HipMlpBroadBf16Heads(arrays, dims, device)
                     return self._heads[key]
                 if backend in ("auto", "hip"):
                     try:

@@ -1,6 +1,7 @@
 """Search rate with the broad HIP heads (heads.HipMlpBroadHeads, Muzero.heads(backend="broad")) against the heads "auto" picks
 for the same fresh net (FusedMlpHeads, the torch GEMMs: these shapes are outside every older HIP layout) on the same step-wise
-BatchedMCTS graph, in one run on one box.
+BatchedMCTS graph, in one run on one box.  --backends chooses the sides: the first one is measured against each of the others
+(--backends broad_bf16,broad,auto: the bf16 broad heads, heads.HipMlpBroadBf16Heads, against both).
 
 Fresh mlp_model nets (obs 6, L 1), K = 2, 50 simulations, MT19937, train=True, graph replays; H in {256, 512} x S in {64, 128} x
 A in {4, 64} x trees in {256, 1024, 4096}.  Per cell both backends build their search and run one warm-up search (which captures
@@ -11,7 +12,7 @@ blocks, (max - min) / median.  Prints one JSON line per measurement and the tabl
 source_sha16 (bench.kernel_source_sha16: the kernel sources the library was built from).
 
     python tools/broad_heads_rate.py [--hidden 256,512] [--state 64,128] [--actions 4,64] [--trees 256,1024,4096] [--sims 50]
-                                     [--window 0.25] [--out FILE]
+                                     [--window 0.25] [--backends broad,auto] [--out FILE]
 """
 import argparse
 import json
@@ -28,7 +29,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def cell(H, S, A, B, sims, window):
+HEADS = {"broad": "HipMlpBroadHeads", "broad_bf16": "HipMlpBroadBf16Heads", "auto": "FusedMlpHeads"}
+
+
+def cell(H, S, A, B, sims, window, backends=("broad", "auto")):
     import stochastic_muzero_amd  # noqa: F401
     mcts, model = import_module("stochastic-muzero_amd.mcts"), import_module("stochastic-muzero_amd.model")
     torch.manual_seed(0)
@@ -36,7 +40,7 @@ def cell(H, S, A, B, sims, window):
                      state_space_dimensions=S, hidden_layer_dimensions=H, number_of_hidden_layer=1)
     obs = torch.randn(B, 6, generator=torch.Generator().manual_seed(1)).cuda()
     sides = []
-    for backend in ("broad", "auto"):
+    for backend in backends:
         heads = m.heads("cuda:0", backend=backend)
         mc = mcts.BatchedMCTS(B, num_simulations=sims, maxium_action_sample=2, rng_mode="mt19937", single_launch=False)
         mc.seed(np.arange(B, dtype=np.uint64))
@@ -67,15 +71,19 @@ def cell(H, S, A, B, sims, window):
 
 
 def table(recs):
-    rows = ["     H    S  actions  trees   broad sims/s   auto (torch) sims/s  broad/auto   broad ms/search  auto ms/search   spread broad / auto"]
+    names = list(dict.fromkeys(r["backend"] for r in recs))
+    first, others = names[0], names[1:]
+    label = lambda n: "auto (torch)" if n == "auto" else n
+    rows = ["     H    S  actions  trees  " + "  ".join(f"{label(n) + ' sims/s':>20}" for n in names) + "  " +
+            "  ".join(f"{first + '/' + n:>16}" for n in others) + "  " + "  ".join(f"{label(n) + ' ms/search':>22}" for n in names) +
+            "   spread " + " / ".join(names)]
     cells = {}
     for r in recs:
         cells.setdefault((r["hidden"], r["state"], r["actions"], r["trees"]), {})[r["backend"]] = r
     for (H, S, A, B), c in cells.items():
-        b, t = c["broad"], c["auto"]
-        rows.append(f'{H:>6}  {S:>3}  {A:>7}  {B:>5}  {b["simulations_per_s"]:>13,}  {t["simulations_per_s"]:>20,}  '
-                    f'{b["simulations_per_s"] / t["simulations_per_s"]:>10.2f}  {b["ms_per_search"]:>16.3f}  {t["ms_per_search"]:>14.3f}   '
-                    f'{b["spread"]:.3f} / {t["spread"]:.3f}')
+        rows.append(f'{H:>6}  {S:>3}  {A:>7}  {B:>5}  ' + "  ".join(f'{c[n]["simulations_per_s"]:>20,}' for n in names) + "  " +
+                    "  ".join(f'{c[first]["simulations_per_s"] / c[n]["simulations_per_s"]:>16.2f}' for n in others) + "  " +
+                    "  ".join(f'{c[n]["ms_per_search"]:>22.3f}' for n in names) + "   " + " / ".join(f'{c[n]["spread"]:.3f}' for n in names))
     return "\n".join(rows)
 
 
@@ -87,21 +95,24 @@ def main():
     ap.add_argument("--trees", default="256,1024,4096")
     ap.add_argument("--sims", type=int, default=50)
     ap.add_argument("--window", type=float, default=0.25)
+    ap.add_argument("--backends", default="broad,auto")
     ap.add_argument("--out")
     a = ap.parse_args()
     import bench
     ints = lambda s: [int(x) for x in s.split(",") if x]
+    backends = [b for b in a.backends.split(",") if b]
+    assert len(backends) >= 2 and set(backends) <= set(HEADS), backends
     recs = []
     for H in ints(a.hidden):
         for S in ints(a.state):
             for A in ints(a.actions):
                 for B in ints(a.trees):
-                    for r in cell(H, S, A, B, a.sims, a.window):
-                        assert r["heads"] == ("HipMlpBroadHeads" if r["backend"] == "broad" else "FusedMlpHeads"), r
+                    for r in cell(H, S, A, B, a.sims, a.window, backends):
+                        assert r["heads"] == HEADS[r["backend"]], r
                         recs.append(r)
                         print(json.dumps(r), flush=True)
     head = (f"# tools/broad_heads_rate.py --hidden {a.hidden} --state {a.state} --actions {a.actions} --trees {a.trees} --sims {a.sims} "
-            f"--window {a.window} ({torch.cuda.get_device_name(0)}; fresh mlp_model nets obs 6 / L 1, K = 2, MT19937, train on, "
+            f"--window {a.window} --backends {a.backends} ({torch.cuda.get_device_name(0)}; fresh mlp_model nets obs 6 / L 1, K = 2, MT19937, train on, "
             f"step-wise graph replays; median of three alternating blocks)\n"
             f"# source_sha16 {bench.kernel_source_sha16()}\n")
     text = head + table(recs) + "\n\n" + "\n".join(json.dumps(r) for r in recs) + "\n"

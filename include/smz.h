@@ -567,7 +567,7 @@ int smz_mlp_recurrent_large(const smz_mlp_desc *desc, const float *weights_dev, 
  *   10 pre_out, 11 apr_out   the policy, a panel matrix of K = H, O = A, at off[m], biases at off[15 + m]; then the value, a
  *                            panel matrix of K = H, O = S, at off[m] + P(A) * R8(H) * 128, biases at off[15 + m] + 128 P(A)
  * The pieces follow one another without gaps: the 15 matrices in index order, then the 15 bias pieces in index order.  The
- * representation matrices are packed in the same form; smz_mlp_recurrent_broad does not read them.
+ * representation matrices are packed in the same form; smz_mlp_recurrent_broad does not read them (smz_mlp_initial_broad does).
  * smz_mlp_recurrent_broad: smz_mlp_recurrent_large's arguments, rows and outputs on such an image, one launch (16-leaf tiles
  * on the matrix cores, a workgroup of four wavefronts per tile sharing every layer's panels, weights streamed from L2; the
  * reductions between the layers and the softmax run across the panels).  A last_action outside [0, A) is evaluated as action
@@ -613,7 +613,7 @@ int smz_mlp_recurrent_broad(const smz_mlp_desc *desc, const float *weights_dev, 
  *   10 pre_out, 11 apr_out   the policy at off[m], biases at off[15 + m]; then the value at off[m] + P(A) * R32(H) * 64, biases
  *                            at off[15 + m] + 128 P(A)
  * The pieces follow one another without gaps: the 15 matrices in index order, then the 15 bias pieces.  The representation
- * matrices are packed in the same form and unused.
+ * matrices are packed in the same form and unused (the root in HIP, smz_mlp_initial_broad, takes a float32 image).
  * smz_mlp_recurrent_broad_bf16: smz_mlp_recurrent_broad's arguments, rows, outputs and promises on such an image (weights_dev:
  * the image).  SMZ_ERR_INVALID, with nothing launched: a null pointer, B < 1, a descriptor smz_mlp_layout_broad_bf16 would
  * not produce (one of smz_mlp_layout_wide, _large or _broad included). */
@@ -636,6 +636,26 @@ int smz_mlp_recurrent_broad_bf16(const smz_mlp_desc *desc, const void *weights_d
 int smz_mlp_initial_wide(const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, float *hidden_out_dev,
                          float *policy_out_dev, int B, smz_stream stream);
 int smz_mlp_initial_large(const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, float *hidden_out_dev,
+                          float *policy_out_dev, int B, smz_stream stream);
+
+/* The ROOT evaluation of the broad family in one launch (csrc/smz_mlp_broad_root.hip): smz_mlp_initial on an image of
+ * smz_mlp_layout_broad, the float32 one -- representation + scale_to_bound_action + root prediction trunk + policy softmax:
+ * obs_dev [B,obs] -> hidden_out_dev [B,S] (scaled), policy_out_dev [B,A] (softmax; while the kernel runs it also parks the
+ * logits there).  No value.  It reads the rep_in / rep_mid / rep_out and pre_in / pre_mid entries and the P(A) policy panels of
+ * pre_out; the image stays as smz_mlp_layout_broad describes it.  The bf16 heads keep a float32 image beside their own for
+ * this call: the root is float32 arithmetic, the contract of smz_mlp_recurrent_broad_bf16 is untouched.
+ * 16-row tiles on the matrix cores, a workgroup of four wavefronts per tile sharing every layer's panels, weights streamed from
+ * L2, at most 64 KB + 32 KB of LDS per workgroup; the minimum / maximum of the scaling and the softmax run across the panels and
+ * are combined in panel order.  Promises:
+ *   - a row's outputs do not depend on the batch it is evaluated in, on its tile mates or on its place in the tile;
+ *   - nothing is written beyond [B,S] and [B,A];
+ *   - no allocation, no host read: safe under stream capture;
+ *   - outputs agree with the float64 evaluation of the networks within the tolerances of smz_mlp_recurrent_wide; they are not
+ *     bit for bit with GEMM-based evaluations.
+ * Refusals, all returned before any HIP call.  SMZ_ERR_INVALID: a null pointer, B < 1, a descriptor smz_mlp_layout_broad would
+ * not produce (one of smz_mlp_layout, _wide, _large or _broad_bf16 included).  SMZ_ERR_TOO_LARGE: obs > 1024 (the observation
+ * tile lives in LDS).  neural_network_mlp_model.py:5-83, muzero_model.py:802-842. */
+int smz_mlp_initial_broad(const smz_mlp_desc *desc, const float *weights_dev, const float *obs_dev, float *hidden_out_dev,
                           float *policy_out_dev, int B, smz_stream stream);
 
 /* ---- synthetic environment + trajectory record (self_play.py:63-98 loop body around the search) -------------- */

@@ -108,6 +108,7 @@ SIGNATURES = {
     "smz_mlp_recurrent_broad_bf16": (C.c_int, [C.POINTER(MlpDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "smz_mlp_initial_wide": (C.c_int, [C.POINTER(MlpDesc), _P, _P, _P, _P, C.c_int, _P]),
     "smz_mlp_initial_large": (C.c_int, [C.POINTER(MlpDesc), _P, _P, _P, _P, C.c_int, _P]),
+    "smz_mlp_initial_broad": (C.c_int, [C.POINTER(MlpDesc), _P, _P, _P, _P, C.c_int, _P]),
     "smz_lstm_layout": (C.c_int, [C.POINTER(LstmDesc)]),
     "smz_lstm_initial": (C.c_int, [C.POINTER(LstmDesc), _P, _P, _P, _P, C.c_int, _P]),
     "smz_lstm_recurrent": (C.c_int, [C.POINTER(LstmDesc), _P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),

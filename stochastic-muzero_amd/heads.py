@@ -251,7 +251,7 @@ class HipMlpHeads(Heads):
         return hidden, reward, policy, value
 
 
-HIP_ROOT_MAX_OBS = 1024     # smz_mlp_initial_wide / _large: the observation tile of a wavefront lives in LDS
+HIP_ROOT_MAX_OBS = 1024     # smz_mlp_initial_wide / _large / _broad: the observation tile lives in LDS
 
 
 class HipRootLimit(ValueError):
@@ -265,13 +265,14 @@ def _check_hip_root(lib, obs, entry):
         raise HipRootLimit(f"hip_root=True: observations of {obs} floats exceed the limit of {HIP_ROOT_MAX_OBS} of {entry}")
 
 
-def _hip_initial(heads, entry, desc, obs):
-    """FusedMlpHeads.initial as ONE launch of `entry` on the packed image, into the same cached h0 / p0 buffers."""
+def _hip_initial(heads, entry, desc, obs, packed=None):
+    """FusedMlpHeads.initial as ONE launch of `entry` on the packed image (heads.packed unless the root has an image of its
+    own), into the same cached h0 / p0 buffers."""
     B = obs.shape[0]
     assert obs.dtype == torch.float32 and obs.is_contiguous() and obs.shape[1] == heads.obs
     hidden, policy = heads._out("h0", (B, heads.S)), heads._out("p0", (B, heads.A))
-    _lib.check(getattr(heads.lib, entry)(C.byref(desc), _ptr(heads.packed), _ptr(obs), _ptr(hidden), _ptr(policy), B,
-                                         _stream(heads.device)))
+    _lib.check(getattr(heads.lib, entry)(C.byref(desc), _ptr(heads.packed if packed is None else packed), _ptr(obs), _ptr(hidden),
+                                         _ptr(policy), B, _stream(heads.device)))
     return hidden, policy
 
 
@@ -395,17 +396,24 @@ class HipMlpBroadHeads(FusedMlpHeads):
     the recurrent networks as ONE hand-written kernel per simulation round (smz_mlp_recurrent_broad, csrc/smz_mlp_broad.hip)
     on the parent's hidden row and the action itself.  Every layer of the packed image (smz_mlp_layout_broad, include/smz.h)
     is a sequence of 128-column panels; the input matrices are a hidden part + an action table.  The root evaluation is
-    FusedMlpHeads.initial, on the torch GEMMs (once per search); no single-launch search takes these heads.  Opt-in
-    (Muzero.heads(backend="broad")).  Raises ValueError outside the kernel's limits."""
+    FusedMlpHeads.initial, on the torch GEMMs (once per search), unless hip_root=True (opt-in): then it is ONE launch on the
+    same packed image (smz_mlp_initial_broad, csrc/smz_mlp_broad_root.hip; observations of up to 1024 floats, ValueError
+    above), equal to the torch root within float32 rounding, not bit for bit.  No single-launch search takes these heads.
+    Opt-in (Muzero.heads(backend="broad")).  Raises ValueError outside the kernel's limits."""
     wants_mlp_input, wants_parent_hidden = False, True
     single_launch = None
 
-    def __init__(self, weights, dims, device):
+    def __init__(self, weights, dims, device, hip_root=False):
         super().__init__(weights, dims, device)
+        self.hip_root = bool(hip_root)
         d = _lib.MlpDesc(int(dims["obs"]), self.A, self.S, self.H, self.L)
         if not hasattr(self.lib, "smz_mlp_layout_broad") or self.lib.smz_mlp_layout_broad(C.byref(d)) != 0:
             raise ValueError("mlp heads outside the limits of the broad tile kernel (H <= 512, S <= 256, A <= 1024)")
         self.broad_desc = d
+        if self.hip_root:
+            _check_hip_root(self.lib, self.obs, "smz_mlp_initial_broad")
+            # (bound on the instance: without the flag `initial` stays FusedMlpHeads.initial itself)
+            self.initial = lambda obs: _hip_initial(self, "smz_mlp_initial_broad", self.broad_desc, obs)
         self.packed = torch.from_numpy(self.pack(weights, d)).to(self.device)
 
     @staticmethod
@@ -462,17 +470,32 @@ class HipMlpBroadBf16Heads(FusedMlpHeads):
     The arithmetic is the contract of include/smz.h, not torch.autocast's: weights rounded to bf16 (nearest even) once, here in
     pack(); every Linear input rounded to bf16 in the kernel; biases, accumulation, ELU, scaling, softmax and support decodes in
     float32; the hidden rows handed back to the tree are unrounded float32.  The root evaluation is FusedMlpHeads.initial, in
-    float32 on the torch GEMMs (once per search); no single-launch search takes these heads.  Opt-in
+    float32 on the torch GEMMs (once per search), unless hip_root=True (opt-in): then it is ONE launch of
+    smz_mlp_initial_broad, still in float32 -- the bf16 contract covers the recurrent networks alone -- on a float32 image
+    of its own, HipMlpBroadHeads.pack on a smz_mlp_layout_broad descriptor (root_desc / root_packed, built only with the
+    flag): the root is bit for bit that of HipMlpBroadHeads.  Extra device memory with the flag: the whole float32 image,
+    a few MB for most shapes, 15 MB at the envelope's corner (obs 1024, A 1024, S 256, H 512; 20 MB with L > 0).  Observations
+    of up to 1024 floats, ValueError above.  No single-launch search takes these heads.  Opt-in
     (Muzero.heads(backend="broad_bf16")).  Raises ValueError outside the kernel's limits."""
     wants_mlp_input, wants_parent_hidden = False, True
     single_launch = None
 
-    def __init__(self, weights, dims, device):
+    def __init__(self, weights, dims, device, hip_root=False):
         super().__init__(weights, dims, device)
+        self.hip_root = bool(hip_root)
         d = _lib.MlpDesc(int(dims["obs"]), self.A, self.S, self.H, self.L)
         if not hasattr(self.lib, "smz_mlp_layout_broad_bf16") or self.lib.smz_mlp_layout_broad_bf16(C.byref(d)) != 0:
             raise ValueError("mlp heads outside the limits of the bf16 broad tile kernel (H <= 512, S <= 256, A <= 1024)")
         self.broad_bf16_desc = d
+        if self.hip_root:
+            _check_hip_root(self.lib, self.obs, "smz_mlp_initial_broad")
+            r = _lib.MlpDesc(int(dims["obs"]), self.A, self.S, self.H, self.L)
+            if self.lib.smz_mlp_layout_broad(C.byref(r)) != 0:
+                raise ValueError("mlp heads outside the limits of the broad tile kernel (H <= 512, S <= 256, A <= 1024)")
+            self.root_desc = r
+            self.root_packed = torch.from_numpy(HipMlpBroadHeads.pack(weights, r)).to(self.device)
+            # (bound on the instance: without the flag `initial` stays FusedMlpHeads.initial itself)
+            self.initial = lambda obs: _hip_initial(self, "smz_mlp_initial_broad", self.root_desc, obs, self.root_packed)
         self.packed = torch.from_numpy(self.pack(weights, d).view("int32")).to(self.device)
 
     @staticmethod

@@ -108,7 +108,7 @@ def mlp_arrays_from_modules(rep, pre, apr, ady, dyn):
 class Muzero:
     """Inference-side stand-in for the reference's Muzero object."""
     heads_backend = "auto"      # what heads(backend=None) resolves to: the loops call heads(device) without a backend
-    hip_root = False            # what heads(hip_root=None) resolves to: the root of the wide / large tile heads in HIP (opt-in)
+    hip_root = False            # what heads(hip_root=None) resolves to: the root of the wide / large / broad tile heads in HIP (opt-in)
 
     def __init__(self, model_structure="mlp_model", observation_space_dimensions=None, action_space_dimensions=None,
                  state_space_dimensions=9, hidden_layer_dimensions=16, number_of_hidden_layer=1, device="cpu",
@@ -283,13 +283,15 @@ class Muzero:
         else (mlp_model) the wide tile kernel for the recurrent networks when the shape is within its limits, else torch;
         "large" (mlp_model, opt-in) = the large-action tile kernel, up to 1024 actions (ValueError outside its limits);
         "broad" (mlp_model, opt-in) = the panel tile kernel for the recurrent networks, hidden_layer_dimensions up to 512 and
-        state_space_dimensions up to 256 (ValueError outside its limits; the root stays on the torch GEMMs);
+        state_space_dimensions up to 256 (ValueError outside its limits; the root stays on the torch GEMMs unless hip_root);
         "broad_bf16" (mlp_model, opt-in) = the same family and limits with bf16 operands on the matrix cores: bf16 weights, every
         Linear input rounded to bf16, float32 elsewhere -- the arithmetic stated in include/smz.h, not torch.autocast's (the root
-        stays in float32 on the torch GEMMs);
+        stays in float32: on the torch GEMMs, or with hip_root in HIP on a float32 image of its own);
         None = self.heads_backend ("auto" unless set).
-        hip_root (opt-in; None = self.hip_root, False unless set): the wide and the large tile heads evaluate the root in ONE
-        HIP launch too (smz_mlp_initial_wide / _large) instead of the torch GEMMs; every other evaluator ignores it.
+        hip_root (opt-in; None = self.hip_root, False unless set): the wide, the large and both broad tile heads evaluate the
+        root in ONE HIP launch too (smz_mlp_initial_wide / _large / _broad) instead of the torch GEMMs -- "broad" and
+        "broad_bf16" used to ignore the flag and now honour it, observations above 1024 floats raising ValueError as for the
+        other two; every other evaluator (the LDS-resident "hip" heads, "torch", the lstm and vision families) ignores it.
         `instance` distinguishes evaluators that must not share output buffers (one per concurrent stream group)."""
         if backend is None:
             backend = self.heads_backend
@@ -311,10 +313,10 @@ class Muzero:
                     self._heads[key] = HipMlpLargeHeads(arrays, dims, device, hip_root=bool(hip_root))
                     return self._heads[key]
                 if backend == "broad":
-                    self._heads[key] = HipMlpBroadHeads(arrays, dims, device)
+                    self._heads[key] = HipMlpBroadHeads(arrays, dims, device, hip_root=bool(hip_root))
                     return self._heads[key]
                 if backend == "broad_bf16":
-                    self._heads[key] = HipMlpBroadBf16Heads(arrays, dims, device)
+                    self._heads[key] = HipMlpBroadBf16Heads(arrays, dims, device, hip_root=bool(hip_root))
                     return self._heads[key]
                 if backend in ("auto", "hip"):
                     try:

@@ -279,8 +279,11 @@ class Muzero:
 
     def heads(self, device, instance=0, backend=None, hip_root=None):
         """Batched evaluator on `device`.  backend: "hip" = the fused LDS-resident HIP kernels (mlp_model and lstm_model when
-        the networks fit a CU's LDS; vision_model), "torch" = torch-ROCm GEMMs + HIP epilogues, "auto" = hip when possible,
-        else (mlp_model) the wide tile kernel for the recurrent networks when the shape is within its limits, else torch;
+        the networks fit a CU's LDS; vision_model with action_space_dimensions, state_space_dimensions and
+        hidden_layer_dimensions up to 64 -- ValueError outside these limits), "torch" = torch-ROCm GEMMs + HIP epilogues,
+        "auto" = hip when possible, else (mlp_model) the wide tile kernel for the recurrent networks when the shape is within
+        its limits, else torch
+        (a vision_model outside the HIP kernels' limits gets its torch modules, ModuleHeads, like the other two families);
         "large" (mlp_model, opt-in) = the large-action tile kernel, up to 1024 actions (ValueError outside its limits);
         "broad" (mlp_model, opt-in) = the panel tile kernel for the recurrent networks, hidden_layer_dimensions up to 512 and
         state_space_dimensions up to 256 (ValueError outside its limits; the root stays on the torch GEMMs unless hip_root);
@@ -345,11 +348,16 @@ class Muzero:
                         if backend == "hip":
                             raise
                 self._heads[key] = LstmTorchHeads(*mods, **kw)
-            elif self.model_structure == "vision_model" and backend in ("auto", "hip"):
-                mods = [getattr(self, f + "_function") for f in _FUNCS[:5]]
-                self._heads[key] = HipVisionHeads(*mods, num_actions=self.action_dimension,
-                                                  support_size=self.state_dimension, device=device)
             else:
+                if self.model_structure == "vision_model" and backend in ("auto", "hip"):
+                    mods = [getattr(self, f + "_function") for f in _FUNCS[:5]]
+                    try:
+                        self._heads[key] = HipVisionHeads(*mods, num_actions=self.action_dimension,
+                                                          support_size=self.state_dimension, device=device)
+                        return self._heads[key]
+                    except ValueError:      # outside the kernels' limits (A, S, H <= 64; the down-sampling family)
+                        if backend == "hip":
+                            raise
                 import copy
                 mods = [copy.deepcopy(getattr(self, f + "_function")) for f in _FUNCS[:5]]
                 self._heads[key] = ModuleHeads(*mods, num_actions=self.action_dimension,

@@ -733,6 +733,52 @@ int smz_host_cartpole_step(double *state_host, const int32_t *action_host, float
  * obs_dev [B][obs_dim] f32 ~ N(0,1), element (env, k) of step t a pure function of (seed, first_env + env, t, k). */
 int smz_synthetic_obs(float *obs_dev, int B, int obs_dim, uint64_t seed, int64_t first_env, int64_t t, smz_stream stream);
 
+/* ---- 2048: a device-resident env WITH chance (csrc/smz_env2048.hip; the rules: csrc/smz_2048.hpp) --------------------- */
+/* Stochastic MuZero's single-player stochastic benchmark: 16 observations, 4 actions, a tile spawn after every move, illegal
+ * moves.  Integer rules, so device, host and any restatement agree bit for bit.
+ *   board      [B][16] u8, row-major exponents: 0 empty, k the tile 2^k (whole bytes: 15 + 15 -> 16 works; domain <= 30).
+ *              One env is 16 bytes, moved as one 128-bit access: board_dev and obs_out_dev must be 16-byte aligned.
+ *   actions    0 up, 1 right, 2 down, 3 left.  Every line slides towards the action's edge; a tile merges at most once per move,
+ *              merges resolve from that edge ([2,2,2,2] -> [4,4,0,0], [2,2,4,0] -> [4,4,0,0], [4,2,2,0] -> [4,4,0,0]).
+ *   reward     the sum of the values of the tiles the move's merges created, float32 (exact).
+ *   legality   a move that leaves the board unchanged is illegal; so is an action outside 0 .. 3 (it indexes nothing).
+ *   spawn      after a legal move: with m empty cells in row-major order, cell number (int)floor(u0 * m) gets exponent 2 when
+ *              u1 < 0.1, else 1.  spawns [B] i32 counts the tiles spawned in the env's current game.
+ *   end        a game is terminated when, after the spawn, no action is legal.
+ *   draws      game_seed = seed + (first_env + e) + 1000003 * episode in uint64 arithmetic (the seed host_envs.HostSlice hands
+ *              to env.reset); spawn number n of a game uses u_c = the counter-based generator's (game_seed, 0, n, c), c = 0, 1:
+ *              n = 0, 1 are the two tiles of the initial board, n = 2 + (legal moves so far) the spawn after a move.
+ *              Independent of the shard and of the launch geometry.
+ *   obs        obs[i] = (float)exponent[i] * 0.0625f (exact).
+ * smz_2048_reset writes the initial boards of game number episode_dev[e] (NULL: 0) of every env, spawns = 2 and, unless
+ * obs_out_dev is NULL, their observations. */
+int smz_2048_reset(uint8_t *board_dev, int32_t *spawns_dev, float *obs_out_dev, uint64_t seed, int64_t first_env,
+                   const int32_t *episode_dev /* NULL = 0 */, int B, smz_stream stream);
+/* One env step of every env in ONE launch (one lane per env): the move, the spawn, the game bookkeeping of smz_episode_ctl and
+ * the trajectory record (smz_traj_pack's layout with obs_dim 16 and A 4: F = 31; traj_dev may be NULL).  ctl is required, and
+ * so is ctl->step_count_dev; ctl->reset_seed and ctl->first_env are the seed and the shard offset of the draws.  The flag is
+ * smz_cartpole_step_ctl's: 0 running | 1 terminated | 2 stopped by ctl->limit | 3 no step (active_dev[e] == 0).
+ * An ILLEGAL move follows the reference (game.py:123-131): board, spawn counter and observation unchanged; reward
+ * min(-(steps so far), -limit, -1) with -limit = -inf when there is no limit; the move counter still advances; the terminated
+ * bit is whatever the current board says.
+ *   on_end 1: a finished env is switched off (active_dev[e] = 0).
+ *   on_end 2: the record keeps the post-step observation; the env gets the initial board of game episode + 1, and spawns and the
+ *             step count restart (obs_out_dev shows the new game's board).
+ *   on_end 0: the env keeps stepping; a dead board then yields illegal-move records.
+ * SMZ_ERR_INVALID, returned before any HIP call: a null board / spawns / action / ctl / step_count pointer, B < 1, on_end 1
+ * without active_dev, on_end 2 without episode_dev, a trajectory without policy / child_visits / root_value or with t outside
+ * [0, T), a misaligned board_dev or obs_out_dev. */
+int smz_2048_step_ctl(uint8_t *board_dev, int32_t *spawns_dev, const int32_t *action_dev, float *obs_out_dev,
+                      float *reward_out_dev, uint8_t *flag_out_dev, const smz_episode_ctl *ctl, double *traj_dev, int T, int t,
+                      const double *policy_dev, const double *child_visits_dev, const float *root_value_dev, int B,
+                      smz_stream stream);
+/* The same rule core compiled for the host, no GPU call (like smz_cartpole_reset_state): one game, one move.  An illegal move
+ * writes nothing to board / spawns and reports reward 0 (its penalty depends on the game's move count: the caller's).
+ * terminated_out: no action is legal on the board as it is after the call.  Outputs may be NULL. */
+int smz_2048_host_reset(uint8_t board[16], int32_t *spawns, uint64_t game_seed);
+int smz_2048_host_step(uint8_t board[16], int32_t *spawns, int action, uint64_t game_seed, float *reward_out,
+                       int *terminated_out, int *illegal_out);
+
 /* Appends one env step of every tree to a fixed-length trajectory buffer laid out [T][B][F] (step-major, so one
  * step is one contiguous, coalesced slab and a finished chunk is one message for the trajectory gather):
  * what Game.policy_step / store_search_statistics append to their lists (game.py:193-195, 263-267).  Record of F =

@@ -1,8 +1,8 @@
 """Vectorised synthetic environments resident on the GPU (the "synthetic fixed-length episodes" of BASELINE.json).
 
 gymnasium is not part of this image, so the environments here are this engine's own: a CartPole-v1 shaped Euler
-integrator (float64 state, float32 observations; physics constants as published for CartPole-v1) and a
-LunarLander-shaped stand-in that only provides observations of the right width.  Env i of a job draws its initial
+integrator (float64 state, float32 observations; physics constants as published for CartPole-v1), the game 2048 (chance
+tile spawns, illegal moves: Board2048Vec) and a LunarLander-shaped stand-in that only provides observations of the right width.  Env i of a job draws its initial
 state from `RandomState(seed).uniform(...)[i]`, so a shard sees exactly the rows it would see in a single-GPU run.
 """
 import ctypes as C
@@ -109,6 +109,77 @@ class CartPoleVec:
         return self.obs, self.reward, self.terminated
 
 
+class Board2048Vec:
+    """B games of 2048 stepped on the device: the built-in env WITH chance (a tile spawns after every move) and with illegal
+    moves -- Stochastic MuZero's own single-player stochastic benchmark.  16 observations (exponent / 16), 4 actions (0 up,
+    1 right, 2 down, 3 left), reward = the values of the tiles a move merges.  Rules, draws and the illegal-move rule:
+    include/smz.h (smz_2048_step_ctl), DESIGN.md section 8.  Integer rules: host_envs.Host2048 under HostVecEnv(env_seed=seed)
+    plays the very same games.
+
+    The attributes and methods of CartPoleVec (on_end / limit as there); the step is a launch of its own behind the search
+    (no `fused_step`).  Env i (global index first_env + i) draws from game_seed = seed + first_env + i + 1000003 * episode, so
+    a shard sees the rows of the single-GPU run.  `board` [B,16] uint8 exponents, `spawns` [B] int32 tiles spawned in the
+    current game."""
+    obs_dim, num_actions = 16, 4
+
+    def __init__(self, num_envs, device, seed=0, first_env=0, total_envs=None, on_end="continue", limit=0):
+        self.lib = _lib.load()
+        self.B, self.device = int(num_envs), torch.device(device)
+        self.seed, self.first_env = int(seed), int(first_env)
+        self.total = int(total_envs) if total_envs is not None else self.first_env + self.B
+        assert on_end in ON_END
+        self.on_end, self.limit = on_end, int(limit)
+        self.board = torch.zeros(self.B, 16, dtype=torch.uint8, device=self.device)
+        self.spawns = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self.obs = torch.zeros(self.B, 16, dtype=torch.float32, device=self.device)
+        self.reward = torch.zeros(self.B, dtype=torch.float32, device=self.device)
+        self.terminated = torch.zeros(self.B, dtype=torch.uint8, device=self.device)     # the flag of the last step
+        self.step_count = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self.episode = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self.active = torch.ones(self.B, dtype=torch.uint8, device=self.device) if on_end == "mask" else None
+        self._ctl = None
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def reset(self):
+        self.terminated.zero_()
+        self.step_count.zero_()
+        self.episode.zero_()
+        if self.active is not None:
+            self.active.fill_(1)
+        P = lambda x: C.c_void_p(x.data_ptr())
+        _lib.check(self.lib.smz_2048_reset(P(self.board), P(self.spawns), P(self.obs), self.seed % (1 << 64), self.first_env,
+                                           None, self.B, self._stream()))
+        return self.obs
+
+    def set_boards(self, boards):
+        """Replaces the boards (tests): [B,16] exponents.  Counters and draws go on from where they are."""
+        b = torch.as_tensor(np.ascontiguousarray(boards, dtype=np.uint8)).reshape(self.B, 16)
+        self.board.copy_(b)
+        self.obs.copy_(self.board.to(torch.float32) * 0.0625)
+
+    def _ctl_struct(self):
+        if self._ctl is None:
+            P = lambda x: None if x is None else x.data_ptr()
+            self._ctl = _lib.EpisodeCtl(P(self.step_count), P(self.episode), P(self.active), self.limit, ON_END[self.on_end],
+                                        self.seed % (1 << 64), self.first_env)
+        return self._ctl
+
+    def step(self, action):
+        """action: int32 [B] device tensor.  Asynchronous on the current stream."""
+        return self.step_and_record(action, None, 0, None, None, None)
+
+    def step_and_record(self, action, chunk_data, t, policy, child_visits, root_value):
+        """step(action) + the trajectory record of this step (smz_traj_pack's layout, F = 31) in one launch."""
+        P = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        T = 0 if chunk_data is None else chunk_data.shape[0]
+        _lib.check(self.lib.smz_2048_step_ctl(P(self.board), P(self.spawns), P(action), P(self.obs), P(self.reward),
+                                              P(self.terminated), C.byref(self._ctl_struct()), P(chunk_data), T, int(t),
+                                              P(policy), P(child_visits), P(root_value), self.B, self._stream()))
+        return self.obs, self.reward, self.terminated
+
+
 class SyntheticVec:
     """Observation-only stand-in (e.g. LunarLander-shaped: obs 8 ~ N(0,1), 4 actions; Box2D is absent here).  The
     observations are generated on the device (smz_synthetic_obs): element (env, k) of step t is a pure function of
@@ -176,7 +247,7 @@ class ImageVec:
         return self.obs, self.reward, self.terminated
 
 
-from .host_envs import HostCartPole, HostCartPoleRender  # noqa: E402,F401  (numpy-only module: the worker processes import it too)
+from .host_envs import HostCartPole, HostCartPoleRender, Host2048, Board2048Batch  # noqa: E402,F401  (numpy-only module: the worker processes import it too)
 from . import host_envs as _he  # noqa: E402
 
 

@@ -189,6 +189,203 @@ class HostCartPoleRender(HostCartPole):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# 2048 on the host: the rules of csrc/smz_2048.hpp and the draws of smz_2048_step_ctl, restated (include/smz.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+_M64 = (1 << 64) - 1
+
+
+def smz_mix64(z):
+    """smz_mix64 (csrc/smz_common.hpp) with Python integers masked to 64 bits."""
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def smz_unit(seed, env, epoch, comp):
+    """smz_unit (csrc/smz_common.hpp): the counter-based generator's draw in [0, 1), the same double as on the device."""
+    z = smz_mix64((smz_mix64((smz_mix64((seed ^ (env * 0xD1342543DE82EF95)) & _M64) + epoch) & _M64) + comp) & _M64)
+    return float(z >> 11) * (1.0 / 9007199254740992.0)
+
+
+def _spawn_2048(board, game_seed, n):
+    """Spawn number n of a game into `board` (16 exponents, row-major): empty cell number floor(u0 * m), exponent 2 when
+    u1 < 0.1, else 1."""
+    empty = [i for i in range(16) if board[i] == 0]
+    if not empty:
+        return
+    u0, u1 = smz_unit(game_seed, 0, n, 0), smz_unit(game_seed, 0, n, 1)
+    board[empty[int(np.floor(u0 * len(empty)))]] = 2 if u1 < 0.1 else 1
+
+
+# cells of line l, from the edge the tiles move towards, for actions 0 up, 1 right, 2 down, 3 left
+_LINES_2048 = ([[4 * j + l for j in range(4)] for l in range(4)], [[4 * l + 3 - j for j in range(4)] for l in range(4)],
+               [[4 * (3 - j) + l for j in range(4)] for l in range(4)], [[4 * l + j for j in range(4)] for l in range(4)])
+
+
+def _dead_2048(board):
+    """No action is legal: an empty board, or a full one without two equal neighbours."""
+    b = np.asarray(board).reshape(4, 4)
+    m = int((b == 0).sum())
+    if 0 < m < 16:
+        return False
+    return m == 16 or not (bool((b[:, 1:] == b[:, :-1]).any()) or bool((b[1:] == b[:-1]).any()))
+
+
+class Host2048:
+    """One game of 2048 on the host behind the gym call shape: the game envs.Board2048Vec plays on the device, rule for rule and
+    draw for draw.  reset(seed=) takes `seed` as the game's seed (spawn number n draws smz_unit(seed, 0, n, c)); an illegal move
+    -- one that leaves the board unchanged, or an action outside 0 .. 3 -- raises ValueError and changes nothing.
+    board: 16 uint8 exponents (0 empty, k the tile 2^k), row-major; observation = exponent / 16."""
+
+    def __init__(self):
+        self.board = np.zeros(16, np.uint8)
+        self.spawns = 0
+        self.game_seed = 0
+
+    def _observation(self):
+        return self.board.astype(np.float32) * np.float32(0.0625)
+
+    def reset(self, seed=None):
+        self.game_seed = int(seed or 0) & _M64
+        b = [0] * 16
+        _spawn_2048(b, self.game_seed, 0)
+        _spawn_2048(b, self.game_seed, 1)
+        self.board[:] = b                                   # (in place: a batch stepper may own the row)
+        self.spawns = 2
+        return self._observation(), {}
+
+    def step(self, action):
+        if not isinstance(action, (int, np.integer)) or not 0 <= int(action) < 4:
+            raise ValueError(f"illegal action {action!r}")
+        old = [int(v) for v in self.board]
+        new, gain = list(old), 0
+        for cells in _LINES_2048[int(action)]:
+            out, free = [], False                           # free: the last tile of `out` may still merge
+            for v in (old[c] for c in cells):
+                if v == 0:
+                    continue
+                if free and out[-1] == v:
+                    out[-1] = v + 1
+                    gain += 1 << (v + 1)
+                    free = False
+                else:
+                    out.append(v)
+                    free = True
+            for c, v in zip(cells, out + [0] * (4 - len(out))):
+                new[c] = v
+        if new == old:
+            raise ValueError(f"illegal move {action!r}: the board does not change")
+        _spawn_2048(new, self.game_seed, self.spawns)
+        self.spawns += 1
+        self.board[:] = new
+        return self._observation(), float(gain), _dead_2048(new), False, {}
+
+    def close(self):
+        pass
+
+    @classmethod
+    def make_batch(cls, envs):
+        return Board2048Batch(envs)
+
+
+def _mix64_array(z):
+    z = z + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def _unit_array(seed, epoch, comp):
+    """smz_unit(seed[i], 0, epoch[i], comp) for uint64 arrays (numpy's uint64 arithmetic wraps like the C one)."""
+    z = _mix64_array(_mix64_array(_mix64_array(seed) + epoch) + np.uint64(comp))
+    return (z >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+
+
+def _slide_lines_2048(lines):
+    """Host2048.step's line rule for an array of lines [m][4] (index 0 = the edge): (new lines, gain per line)."""
+    order = np.argsort(lines == 0, axis=1, kind="stable")                # tiles to the front, in order
+    v = np.take_along_axis(lines, order, 1).astype(np.int64)
+    a, b, c, d = v[:, 0], v[:, 1], v[:, 2], v[:, 3]
+    m1 = (a == b) & (a != 0)
+    m1b = m1 & (c == d) & (c != 0)                                       # the second merge behind a first one
+    m2 = ~m1 & (b == c) & (b != 0)
+    m3 = ~m1 & ~m2 & (c == d) & (c != 0)
+    out = np.stack([np.where(m1, a + 1, a),
+                    np.where(m1, np.where(m1b, c + 1, c), np.where(m2, b + 1, b)),
+                    np.where(m1, np.where(m1b, 0, d), np.where(m2, d, np.where(m3, c + 1, c))),
+                    np.where(m1 | m2 | m3, 0, d)], 1)
+    gain = m1 * (1 << (a + 1)) + m1b * (1 << (c + 1)) + m2 * (1 << (b + 1)) + m3 * (1 << (c + 1))
+    return out.astype(np.uint8), gain
+
+
+def _as_lines_2048(grid, action):
+    """View of boards [m][4][4] whose [m][l] is line l from the edge `action` moves towards."""
+    g = grid.transpose(0, 2, 1) if action in (0, 2) else grid
+    return g[:, :, ::-1] if action in (1, 2) else g
+
+
+class Board2048Batch:
+    """Host2048.step for a whole slice at once (the make_batch / reset_one / step_batch protocol of CartPoleBatch): the boards
+    of the slice's n envs are ONE [n][16] uint8 array (every env object's `board` becomes a row view of it) and a step is a
+    fixed number of numpy operations.  Same rules, same draws: the per-env class is the checker (tests/test_env2048.py)."""
+
+    def __init__(self, envs):
+        self.envs = list(envs)
+        n = len(self.envs)
+        self.board = np.zeros((n, 16), np.uint8)
+        self.spawns = np.zeros(n, np.int64)
+        self.game_seed = np.zeros(n, np.uint64)
+        for i, e in enumerate(self.envs):
+            self.board[i] = e.board
+            self.spawns[i], self.game_seed[i] = e.spawns, e.game_seed
+            e.board = self.board[i]                         # a view; the spawn counters of stepped games live here, in `spawns`
+
+    def reset_one(self, i, seed):
+        obs, _ = self.envs[i].reset(seed=seed)              # (writes through the row view)
+        self.spawns[i], self.game_seed[i] = self.envs[i].spawns, self.envs[i].game_seed
+        return obs
+
+    def step_batch(self, actions, go):
+        n = len(self.envs)
+        actions = np.asarray(actions, np.int64)
+        old = self.board.copy()
+        new = old.copy().reshape(n, 4, 4)
+        reward = np.zeros(n)
+        for a in range(4):
+            idx = np.nonzero(go & (actions == a))[0]
+            if not len(idx):
+                continue
+            grid = old[idx].reshape(-1, 4, 4)
+            out, gain = _slide_lines_2048(np.ascontiguousarray(_as_lines_2048(grid, a)).reshape(-1, 4))
+            res = np.empty_like(grid)
+            _as_lines_2048(res, a)[...] = out.reshape(-1, 4, 4)
+            new[idx] = res
+            reward[idx] = gain.reshape(-1, 4).sum(1)
+        new = new.reshape(n, 16)
+        moved = go & (new != old).any(1)
+        illegal = go & ~moved
+        idx = np.nonzero(moved)[0]
+        if len(idx):
+            b = new[idx]
+            empty = b == 0
+            m = empty.sum(1)
+            epoch = self.spawns[idx].astype(np.uint64)
+            u0, u1 = _unit_array(self.game_seed[idx], epoch, 0), _unit_array(self.game_seed[idx], epoch, 1)
+            k = np.floor(u0 * m).astype(np.int64)
+            cell = np.argmax(empty & (np.cumsum(empty, 1) - 1 == k[:, None]), 1)
+            b[np.arange(len(idx)), cell] = np.where(u1 < 0.1, 2, 1)
+            self.board[idx] = b
+            self.spawns[idx] += 1
+        g =self.board.reshape(n, 4, 4)
+        m = (g == 0).sum((1, 2))
+        pair = (g[:, :, 1:] == g[:, :, :-1]).any((1, 2)) | (g[:, 1:] == g[:, :-1]).any((1, 2))
+        term = (m == 16) | ((m == 0) & ~pair)
+        reward[~moved] = 0.0
+        return self.board.astype(np.float32) * np.float32(0.0625), reward, term, illegal
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # observation adapters: what of env.reset / env.step's observation goes into the env's row
 # ---------------------------------------------------------------------------------------------------------------------------
 def tap_index(n_in, n_out):

@@ -779,6 +779,54 @@ int smz_2048_host_reset(uint8_t board[16], int32_t *spawns, uint64_t game_seed);
 int smz_2048_host_step(uint8_t board[16], int32_t *spawns, int action, uint64_t game_seed, float *reward_out,
                        int *terminated_out, int *illegal_out);
 
+/* ---- Connect Four: a device-resident env with TWO players (csrc/smz_envconnect4.hip; the rules: csrc/smz_connect4.hpp) --- */
+/* Integer rules, so device, host and any restatement agree bit for bit.
+ *   board      6 rows x 7 columns.
+ *   state      discs [B][2] u64, 16 bytes per env, moved as one 128-bit access: discs_dev must be 16-byte aligned.  Word p holds
+ *              player p's discs.
+ *   bit layout bit 7 * c + r is column c, row r; r = 0 is the bottom row.  Bit 6 of every column's 7-bit group is a sentinel and
+ *              never set: it keeps lines from wrapping between columns.
+ *   to move    read off the board: colour popcount(discs[0] | discs[1]) & 1.  Colour 0 moves first on the empty board.
+ *   actions    0 .. 6: drop a disc of the side to move into that column.
+ *   height     of column c: popcount((all >> 7c) & 0x3f).
+ *   illegal    a full column (height 6), an action outside 0 .. 6, and any action on a finished board.
+ *   win        four in a row for the side that just moved: m = b & (b >> s); m & (m >> 2s) for s = 1, 7, 6, 8.
+ *   end        terminated when the move wins or the board holds 42 discs.  A board that already has a line or is full is
+ *              finished.
+ *   reward     +1.0f for a winning move, otherwise 0.0f.  A draw gives 0.
+ *   obs        43 float32, exact.  obs[7 * r + c] is +1 for a colour-0 disc, -1 for a colour-1 disc, 0 when empty; obs[42] is +1
+ *              when colour 0 is to move on this board, else -1.  A pure function of the board.
+ *   reset      the empty board.  The game is deterministic: the env makes no draws (ctl->reset_seed and ctl->first_env are
+ *              accepted for the common shape and unused).
+ * smz_connect4_reset writes the empty boards and, unless obs_out_dev is NULL, their observations. */
+int smz_connect4_reset(uint64_t *discs_dev, float *obs_out_dev, int B, smz_stream stream);
+/* One env step of every env in ONE launch (one lane per env, one wavefront per workgroup): the move, the win test, the game
+ * bookkeeping of smz_episode_ctl and the trajectory record (smz_traj_pack's layout with obs_dim 43 and A 7: F = 67; traj_dev may
+ * be NULL).  ctl is required, and so is ctl->step_count_dev.  The flag is smz_cartpole_step_ctl's: 0 running | 1 terminated |
+ * 2 stopped by ctl->limit | 3 no step (active_dev[e] == 0).  The observation rows and the record rows of a workgroup are built
+ * in LDS and written as contiguous runs; obs_out_dev gets the row of EVERY env, switched-off ones included (a pure function
+ * of the board).
+ * An ILLEGAL move follows the reference (game.py:123-131): board and observation unchanged; reward
+ * min(-(steps so far), -limit, -1) with -limit = -inf when there is no limit; the move counter still advances; the terminated
+ * bit is whatever the current board says.  The search's root player is the move counter modulo the cycle, the disc colour comes
+ * from the board: after an illegal move the two disagree for the rest of that game, as in the reference with any two-player
+ * env that raises on an illegal move.
+ *   on_end 1: a finished env is switched off (active_dev[e] = 0).
+ *   on_end 2: the record keeps the finished board's observation; the env starts game episode + 1 from the empty board and the
+ *             step count restarts (obs_out_dev shows the empty board).
+ *   on_end 0: the env keeps stepping; a finished board then yields illegal-move records.
+ * SMZ_ERR_INVALID, returned before any HIP call: a null discs / action / ctl / step_count pointer, B < 1, on_end 1 without
+ * active_dev, on_end 2 without episode_dev, a trajectory without policy / child_visits / root_value or with t outside [0, T),
+ * a misaligned discs_dev. */
+int smz_connect4_step_ctl(uint64_t *discs_dev, const int32_t *action_dev, float *obs_out_dev, float *reward_out_dev,
+                          uint8_t *flag_out_dev, const smz_episode_ctl *ctl, double *traj_dev, int T, int t,
+                          const double *policy_dev, const double *child_visits_dev, const float *root_value_dev, int B,
+                          smz_stream stream);
+/* The same rule core compiled for the host, no GPU call: one game, one move.  An illegal move writes nothing and reports
+ * reward 0 (its penalty depends on the game's move count: the caller's).  terminated_out: the board as it is after the call is
+ * finished.  Outputs may be NULL. */
+int smz_connect4_host_step(uint64_t discs[2], int action, float *reward_out, int *terminated_out, int *illegal_out);
+
 /* Appends one env step of every tree to a fixed-length trajectory buffer laid out [T][B][F] (step-major, so one
  * step is one contiguous, coalesced slab and a finished chunk is one message for the trajectory gather):
  * what Game.policy_step / store_search_statistics append to their lists (game.py:193-195, 263-267).  Record of F =

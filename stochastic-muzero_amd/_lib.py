@@ -145,6 +145,10 @@ SIGNATURES = {
     "smz_2048_host_reset": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_uint64]),
     "smz_2048_host_step": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_int),
                                      C.POINTER(C.c_int)]),
+    "smz_connect4_reset": (C.c_int, [_P, _P, C.c_int, _P]),
+    "smz_connect4_step_ctl": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(EpisodeCtl), _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P]),
+    "smz_connect4_host_step": (C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int)]),
     "smz_set_active": (C.c_int, [_P, _P]),
     "smz_set_players": (C.c_int, [_P, C.c_int, _P, _P]),
     "smz_set_leaf_ids_out": (C.c_int, [_P, _P]),

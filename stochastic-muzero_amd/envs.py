@@ -2,7 +2,7 @@
 
 gymnasium is not part of this image, so the environments here are this engine's own: a CartPole-v1 shaped Euler
 integrator (float64 state, float32 observations; physics constants as published for CartPole-v1), the game 2048 (chance
-tile spawns, illegal moves: Board2048Vec) and a LunarLander-shaped stand-in that only provides observations of the right width.  Env i of a job draws its initial
+tile spawns, illegal moves: Board2048Vec), the two-player game Connect Four (Connect4Vec) and a LunarLander-shaped stand-in that only provides observations of the right width.  Env i of a job draws its initial
 state from `RandomState(seed).uniform(...)[i]`, so a shard sees exactly the rows it would see in a single-GPU run.
 """
 import ctypes as C
@@ -180,6 +180,79 @@ class Board2048Vec:
         return self.obs, self.reward, self.terminated
 
 
+class Connect4Vec:
+    """B games of Connect Four stepped on the device: the built-in env with TWO players.  6 rows x 7 columns, 7 actions (drop a
+    disc into column 0 .. 6), 43 observations (+1 a colour-0 disc, -1 a colour-1 disc, 0 empty, row-major from the bottom row;
+    obs[42] = +1 when colour 0 is to move, else -1), reward +1 for the move that makes four in a row, 0 otherwise (a draw
+    included).  Full columns, actions outside 0 .. 6 and moves on a finished board are illegal, under the reference's rule.
+    Rules and bit layout: include/smz.h (smz_connect4_step_ctl), DESIGN.md section 8.2.  Integer rules and no draws:
+    host_envs.HostConnect4 under HostVecEnv plays the very same games.
+
+    The side to move is read off the board; a multi-player search takes its root player from `step_count` (selfplay), and the
+    two agree until a game's first illegal move.
+
+    The attributes and methods of Board2048Vec (on_end / limit as there); the step is a launch of its own behind the search
+    (no `fused_step`).  `seed`, `first_env` and `total_envs` are accepted for the common constructor shape: the game is
+    deterministic, so a shard sees the rows of the single-GPU run whatever they are.  `discs` [B,2] uint64 as two int64 words:
+    word p = the discs of colour p, bit 7 * c + r = column c, row r."""
+    obs_dim, num_actions = 43, 7
+
+    def __init__(self, num_envs, device, seed=0, first_env=0, total_envs=None, on_end="continue", limit=0):
+        self.lib = _lib.load()
+        self.B, self.device = int(num_envs), torch.device(device)
+        self.seed, self.first_env = int(seed), int(first_env)
+        self.total = int(total_envs) if total_envs is not None else self.first_env + self.B
+        assert on_end in ON_END
+        self.on_end, self.limit = on_end, int(limit)
+        self.discs = torch.zeros(self.B, 2, dtype=torch.int64, device=self.device)      # (the bits of uint64 words; bit 63 unused)
+        self.obs = torch.zeros(self.B, 43, dtype=torch.float32, device=self.device)
+        self.reward = torch.zeros(self.B, dtype=torch.float32, device=self.device)
+        self.terminated = torch.zeros(self.B, dtype=torch.uint8, device=self.device)     # the flag of the last step
+        self.step_count = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self.episode = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self.active = torch.ones(self.B, dtype=torch.uint8, device=self.device) if on_end == "mask" else None
+        self._ctl = None
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def reset(self):
+        self.terminated.zero_()
+        self.step_count.zero_()
+        self.episode.zero_()
+        if self.active is not None:
+            self.active.fill_(1)
+        P = lambda x: C.c_void_p(x.data_ptr())
+        _lib.check(self.lib.smz_connect4_reset(P(self.discs), P(self.obs), self.B, self._stream()))
+        return self.obs
+
+    def set_boards(self, discs):
+        """Replaces the positions (tests): [B,2] uint64 words.  The counters go on from where they are."""
+        d = np.ascontiguousarray(discs, dtype=np.uint64).reshape(self.B, 2)
+        self.discs.copy_(torch.from_numpy(d.view(np.int64)))
+        self.obs.copy_(torch.from_numpy(_he.connect4_observations(d)))
+
+    def _ctl_struct(self):
+        if self._ctl is None:
+            P = lambda x: None if x is None else x.data_ptr()
+            self._ctl = _lib.EpisodeCtl(P(self.step_count), P(self.episode), P(self.active), self.limit, ON_END[self.on_end],
+                                        self.seed % (1 << 64), self.first_env)
+        return self._ctl
+
+    def step(self, action):
+        """action: int32 [B] device tensor.  Asynchronous on the current stream."""
+        return self.step_and_record(action, None, 0, None, None, None)
+
+    def step_and_record(self, action, chunk_data, t, policy, child_visits, root_value):
+        """step(action) + the trajectory record of this step (smz_traj_pack's layout, F = 67) in one launch."""
+        P = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        T = 0 if chunk_data is None else chunk_data.shape[0]
+        _lib.check(self.lib.smz_connect4_step_ctl(P(self.discs), P(action), P(self.obs), P(self.reward), P(self.terminated),
+                                                  C.byref(self._ctl_struct()), P(chunk_data), T, int(t), P(policy),
+                                                  P(child_visits), P(root_value), self.B, self._stream()))
+        return self.obs, self.reward, self.terminated
+
+
 class SyntheticVec:
     """Observation-only stand-in (e.g. LunarLander-shaped: obs 8 ~ N(0,1), 4 actions; Box2D is absent here).  The
     observations are generated on the device (smz_synthetic_obs): element (env, k) of step t is a pure function of
@@ -247,7 +320,7 @@ class ImageVec:
         return self.obs, self.reward, self.terminated
 
 
-from .host_envs import HostCartPole, HostCartPoleRender, Host2048, Board2048Batch  # noqa: E402,F401  (numpy-only module: the worker processes import it too)
+from .host_envs import HostCartPole, HostCartPoleRender, Host2048, Board2048Batch, HostConnect4, Connect4Batch  # noqa: E402,F401  (numpy-only module: the worker processes import it too)
 from . import host_envs as _he  # noqa: E402
 
 

@@ -386,6 +386,125 @@ class Board2048Batch:
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# Connect Four on the host: the rules of csrc/smz_connect4.hpp, restated (include/smz.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+_C4_SHIFTS = np.array([7 * c + r for r in range(6) for c in range(7)], np.uint64)       # bit of observation cell 7 * r + c
+_C4_LINE_SHIFTS = (1, 7, 6, 8)                                                           # vertical, horizontal, the two diagonals
+
+
+def _c4_line(b):
+    """Four in a row in the discs of one colour: a Python integer, or a uint64 array (then an array of bools)."""
+    hit = b & 0
+    for s in _C4_LINE_SHIFTS:
+        if isinstance(b, np.ndarray):
+            m = b & (b >> np.uint64(s))
+            hit = hit | (m & (m >> np.uint64(2 * s)))
+        else:
+            m = b & (b >> s)
+            hit |= m & (m >> (2 * s))
+    return hit != 0
+
+
+def _c4_popcount(x):
+    """Set bits of every word of a uint64 array (the usual pairwise sums; numpy's uint64 arithmetic wraps like the C one)."""
+    x = x - ((x >> np.uint64(1)) & np.uint64(0x5555555555555555))
+    x = (x & np.uint64(0x3333333333333333)) + ((x >> np.uint64(2)) & np.uint64(0x3333333333333333))
+    x = (x + (x >> np.uint64(4))) & np.uint64(0x0F0F0F0F0F0F0F0F)
+    return ((x * np.uint64(0x0101010101010101)) >> np.uint64(56)).astype(np.int64)
+
+
+def connect4_observations(discs):
+    """[n][2] uint64 positions -> [n][43] float32 observations: obs[7 * r + c] = +1 / -1 / 0 for a colour-0 disc, a colour-1 disc,
+    an empty cell (r = 0 the bottom row); obs[42] = +1 when colour 0 is to move, else -1."""
+    d = np.asarray(discs, np.uint64).reshape(-1, 2)
+    obs = np.empty((len(d), 43), np.float32)
+    one = np.uint64(1)
+    obs[:, :42] = ((d[:, :1] >> _C4_SHIFTS) & one).astype(np.float32) - ((d[:, 1:] >> _C4_SHIFTS) & one).astype(np.float32)
+    obs[:, 42] = np.where(_c4_popcount(d[:, 0] | d[:, 1]) & 1, -1.0, 1.0)
+    return obs
+
+
+class HostConnect4:
+    """One game of Connect Four on the host behind the gym call shape: the game envs.Connect4Vec plays on the device, rule for
+    rule.  The game is deterministic: reset(seed=) ignores the seed.  An illegal move -- a full column, an action outside
+    0 .. 6, any move on a finished board -- raises ValueError and changes nothing.
+    discs: 2 uint64 words, word p = the discs of colour p, bit 7 * c + r = column c, row r (r = 0 the bottom row)."""
+
+    def __init__(self):
+        self.discs = np.zeros(2, np.uint64)
+
+    def _observation(self):
+        return connect4_observations(self.discs)[0]
+
+    def reset(self, seed=None):
+        self.discs[:] = 0                                   # (in place: a batch stepper may own the row)
+        return self._observation(), {}
+
+    def step(self, action):
+        if not isinstance(action, (int, np.integer)) or not 0 <= int(action) < 7:
+            raise ValueError(f"illegal action {action!r}")
+        d = [int(self.discs[0]), int(self.discs[1])]
+        both = d[0] | d[1]
+        count = bin(both).count("1")
+        if _c4_line(d[0]) or _c4_line(d[1]) or count == 42:
+            raise ValueError(f"illegal move {action!r}: the game is over")
+        height = bin((both >> (7 * int(action))) & 0x3F).count("1")
+        if height >= 6:
+            raise ValueError(f"illegal move {action!r}: the column is full")
+        colour = count & 1
+        d[colour] |= 1 << (7 * int(action) + height)
+        self.discs[colour] = d[colour]
+        won = bool(_c4_line(d[colour]))
+        return self._observation(), 1.0 if won else 0.0, won or count + 1 == 42, False, {}
+
+    def close(self):
+        pass
+
+    @classmethod
+    def make_batch(cls, envs):
+        return Connect4Batch(envs)
+
+
+class Connect4Batch:
+    """HostConnect4.step for a whole slice at once (the make_batch / reset_one / step_batch protocol of CartPoleBatch): the
+    positions of the slice's n envs are ONE [n][2] uint64 array (every env object's `discs` becomes a row view of it) and a step
+    is a fixed number of numpy operations on uint64 arrays.  Same rules: the per-env class is the checker
+    (tests/test_envconnect4.py)."""
+
+    def __init__(self, envs):
+        self.envs = list(envs)
+        n = len(self.envs)
+        self.discs = np.zeros((n, 2), np.uint64)
+        for i, e in enumerate(self.envs):
+            self.discs[i] = e.discs
+            e.discs = self.discs[i]                         # a view
+
+    def reset_one(self, i, seed):
+        obs, _ = self.envs[i].reset(seed=seed)              # (writes through the row view)
+        return obs
+
+    def step_batch(self, actions, go):
+        actions = np.asarray(actions, np.int64)
+        d = self.discs
+        both = d[:, 0] | d[:, 1]
+        count = _c4_popcount(both)
+        finished = _c4_line(d[:, 0]) | _c4_line(d[:, 1]) | (count == 42)
+        in_range = (actions >= 0) & (actions < 7)
+        column = np.where(in_range, actions, 0).astype(np.uint64) * np.uint64(7)
+        height = _c4_popcount((both >> column) & np.uint64(0x3F))
+        moved = np.asarray(go, bool) & in_range & ~finished & (height < 6)
+        illegal = np.asarray(go, bool) & ~moved
+        bit = np.where(moved, np.uint64(1) << (column + np.minimum(height, 5).astype(np.uint64)), np.uint64(0))
+        second = (count & 1).astype(bool)
+        mine = np.where(second, d[:, 1], d[:, 0]) | bit
+        d[:, 0] = np.where(second, d[:, 0], mine)
+        d[:, 1] = np.where(second, mine, d[:, 1])
+        won = moved & _c4_line(mine)
+        term = np.where(moved, won | (count + 1 == 42), finished)
+        return connect4_observations(d), won.astype(np.float64), term, illegal
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # observation adapters: what of env.reset / env.step's observation goes into the env's row
 # ---------------------------------------------------------------------------------------------------------------------------
 def tap_index(n_in, n_out):

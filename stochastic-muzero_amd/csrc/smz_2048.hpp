@@ -142,13 +142,4 @@ SMZ_2048_HD inline void store(const uint32_t w[4], uint8_t b[16]) {
     for (int i = 0; i < 16; i++) b[i] = (uint8_t)((w[i >> 2] >> (8 * (i & 3))) & 255u);
 }
 
-// The reward of an illegal move (game.py:123-131): min(-(steps so far), -limit, -1), -limit = -inf without a limit.
-SMZ_2048_HD inline float illegal_reward(int steps_so_far, int limit) {
-    float r = -(float)steps_so_far;
-    const float l = limit > 0 ? -(float)limit : -INFINITY;
-    if (l < r) r = l;
-    if (-1.0f < r) r = -1.0f;
-    return r;
-}
-
 }  // namespace smz2048

@@ -78,13 +78,4 @@ SMZ_C4_HD inline float cell_obs(uint64_t d0, uint64_t d1, int r, int c) {
 // obs[42]: +1 when colour 0 is to move, else -1
 SMZ_C4_HD inline float mover_obs(uint64_t d0, uint64_t d1) { return to_move(d0, d1) ? -1.0f : 1.0f; }
 
-// The reward of an illegal move (game.py:123-131): min(-(steps so far), -limit, -1), -limit = -inf without a limit.
-SMZ_C4_HD inline float illegal_reward(int steps_so_far, int limit) {
-    float r = -(float)steps_so_far;
-    const float l = limit > 0 ? -(float)limit : -INFINITY;
-    if (l < r) r = l;
-    if (-1.0f < r) r = -1.0f;
-    return r;
-}
-
 }  // namespace smzc4

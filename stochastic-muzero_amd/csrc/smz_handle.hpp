@@ -92,6 +92,15 @@ int launch_check() {
     return SMZ_OK;
 }
 
+// What every entry point that takes a smz_episode_ctl (non-null) requires of it; the refusal is in the last-error text.
+bool episode_ctl_ok(const char *who, const smz_episode_ctl *c) {
+    if (c->step_count_dev && c->on_end >= 0 && c->on_end <= 2 && !(c->on_end == 2 && !c->episode_dev) &&
+        !(c->on_end == 1 && !c->active_dev))
+        return true;
+    fail(SMZ_ERR_INVALID, "%s: bad smz_episode_ctl: it needs step_count_dev, on_end 1 needs active_dev, on_end 2 needs episode_dev", who);
+    return false;
+}
+
 // ---- the host path the single-launch searches share ----
 // Refusals that are word for word the same in every search; `who` is the entry point or launcher the message names.
 int refuse_large_actions(const char *who) { return fail(SMZ_ERR_TOO_LARGE, "%s: large-action handles search step-wise only", who); }

@@ -701,10 +701,8 @@ int smz_cartpole_step_ctl(double *state_dev, const int32_t *action_dev, float *o
                           uint8_t *flag_out_dev, const smz_episode_ctl *ctl, double *traj_dev, int T, int t,
                           const double *policy_dev, const double *child_visits_dev, const float *root_value_dev, int B,
                           smz_stream stream) {
-    if (!state_dev || !action_dev || !ctl || !ctl->step_count_dev || B < 1)
-        return fail(SMZ_ERR_INVALID, "smz_cartpole_step_ctl: bad argument%s");
-    if (ctl->on_end < 0 || ctl->on_end > 2 || (ctl->on_end == 2 && !ctl->episode_dev) || (ctl->on_end == 1 && !ctl->active_dev))
-        return fail(SMZ_ERR_INVALID, "smz_cartpole_step_ctl: on_end 1 needs active_dev, on_end 2 needs episode_dev%s");
+    if (!state_dev || !action_dev || !ctl || B < 1) return fail(SMZ_ERR_INVALID, "smz_cartpole_step_ctl: bad argument%s");
+    if (!episode_ctl_ok("smz_cartpole_step_ctl", ctl)) return SMZ_ERR_INVALID;
     if (traj_dev && (!policy_dev || !child_visits_dev || !root_value_dev || t < 0 || t >= T))
         return fail(SMZ_ERR_INVALID, "smz_cartpole_step_ctl: bad trajectory argument%s");
     const EnvStep E = {state_dev, obs_out_dev, reward_out_dev, flag_out_dev, ctl->step_count_dev, ctl->episode_dev,

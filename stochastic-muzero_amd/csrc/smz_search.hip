@@ -102,9 +102,7 @@ int smz_search_mlp_act_cartpole(smz_handle *h, const smz_mlp_desc *desc, const f
         return fail(SMZ_ERR_INVALID, "smz_search_mlp_act_cartpole: the built-in env has 4 observations and 2 actions%s");
     if (h->P.n_cycle > 1) return refuse_multi_player("smz_search_mlp_act_cartpole");
     const smz_episode_ctl *c = env->ctl;
-    if (c && (!c->step_count_dev || c->on_end < 0 || c->on_end > 2 || (c->on_end == 2 && !c->episode_dev) ||
-              (c->on_end == 1 && !c->active_dev)))
-        return fail(SMZ_ERR_INVALID, "smz_search_mlp_act_cartpole: bad smz_episode_ctl (as smz_cartpole_step_ctl)%s");
+    if (c && !episode_ctl_ok("smz_search_mlp_act_cartpole", c)) return SMZ_ERR_INVALID;
     if ((c ? c->active_dev : nullptr) != h->P.active)
         return fail(SMZ_ERR_INVALID, "smz_search_mlp_act_cartpole: ctl->active_dev must be the array given to smz_set_active%s");
     if (env->traj_dev && (env->t < 0 || env->t >= env->T))

@@ -19,18 +19,25 @@ from . import _lib
 ON_END = {"continue": 0, "mask": 1, "reset": 2}
 
 
-class CartPoleVec:
-    """B CartPole-v1 shaped games stepped on the device.
+def _ptr(x):
+    return None if x is None else C.c_void_p(x.data_ptr())
+
+
+class _DeviceEnvVec:
+    """What the envs stepped on the device share: the constructor, the outputs of a step (`obs`, `reward`, `terminated`: the flag
+    of the last step) and the game bookkeeping of smz_episode_ctl (`step_count`, `episode`, `active`).
 
     on_end says what happens to an env whose game is over (terminated, or `limit` steps played -- the two exits of the
     reference's loop, self_play.py:79):
       "continue"  keep stepping (the fixed-length synthetic episodes of the benchmark; flags are recorded, nothing else);
       "mask"      switch the env off: `active[e]` drops to 0 on the device, the search skips it from then on
                   (SearchEngine.set_active) and its later records carry flag 3;
-      "reset"     start its next game at once (counter-based reset state, smz_cartpole_step_ctl), so that every
-                  simulation of a chunk belongs to some game.
-    """
-    obs_dim, num_actions = 4, 2
+      "reset"     start its next game at once, so that every simulation of a chunk belongs to some game.
+
+    A game states `obs_dim`, `num_actions`, `_step_name` (its *_step_ctl entry point: the state pointers, then the common
+    argument list), `_alloc_state()` (its state tensors), `_state_ptrs()` and `reset()`."""
+    obs_dim = num_actions = _step_name = None
+    _zeroed = True                               # the outputs of a step are allocated zeroed (CartPole's: uninitialised)
 
     def __init__(self, num_envs, device, seed=0, first_env=0, total_envs=None, on_end="continue", limit=0):
         self.lib = _lib.load()
@@ -39,25 +46,75 @@ class CartPoleVec:
         self.total = int(total_envs) if total_envs is not None else self.first_env + self.B
         assert on_end in ON_END
         self.on_end, self.limit = on_end, int(limit)
-        self.state = torch.empty(self.B, 4, dtype=torch.float64, device=self.device)
-        self.obs = torch.empty(self.B, 4, dtype=torch.float32, device=self.device)
-        self.reward = torch.empty(self.B, dtype=torch.float32, device=self.device)
-        self.terminated = torch.empty(self.B, dtype=torch.uint8, device=self.device)     # the flag of the last step
+        self._alloc_state()
+        new = torch.zeros if self._zeroed else torch.empty
+        self.obs = new(self.B, self.obs_dim, dtype=torch.float32, device=self.device)
+        self.reward = new(self.B, dtype=torch.float32, device=self.device)
+        self.terminated = new(self.B, dtype=torch.uint8, device=self.device)     # the flag of the last step
         self.step_count = torch.zeros(self.B, dtype=torch.int32, device=self.device)
         self.episode = torch.zeros(self.B, dtype=torch.int32, device=self.device)
         self.active = torch.ones(self.B, dtype=torch.uint8, device=self.device) if on_end == "mask" else None
+        self._step_fn = getattr(self.lib, self._step_name)
         self._ctl = None
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _reset_counters(self):
+        self.terminated.zero_()
+        self.step_count.zero_()
+        self.episode.zero_()
+        if self.active is not None:
+            self.active.fill_(1)
+
+    def _controlled(self):
+        return self.on_end != "continue" or self.limit > 0
+
+    def _reset_seed(self):
+        return self.seed % (1 << 64)
+
+    def _ctl_struct(self):
+        if self._ctl is None:
+            P = lambda x: None if x is None else x.data_ptr()
+            self._ctl = _lib.EpisodeCtl(P(self.step_count), P(self.episode), P(self.active), self.limit, ON_END[self.on_end],
+                                        self._reset_seed(), self.first_env)
+        return self._ctl
+
+    def step(self, action):
+        """action: int32 [B] device tensor.  Asynchronous on the current stream."""
+        return self.step_and_record(action, None, 0, None, None, None)
+
+    def step_and_record(self, action, chunk_data, t, policy, child_visits, root_value):
+        """step(action) + the trajectory record of this step (smz_traj_pack's layout) in one launch."""
+        T = 0 if chunk_data is None else chunk_data.shape[0]
+        _lib.check(self._step_fn(*self._state_ptrs(), _ptr(action), _ptr(self.obs), _ptr(self.reward), _ptr(self.terminated),
+                                 C.byref(self._ctl_struct()), _ptr(chunk_data), T, int(t), _ptr(policy), _ptr(child_visits),
+                                 _ptr(root_value), self.B, self._stream()))
+        return self.obs, self.reward, self.terminated
+
+
+class CartPoleVec(_DeviceEnvVec):
+    """B CartPole-v1 shaped games stepped on the device (on_end / limit: _DeviceEnvVec; "reset" draws the next game's state from
+    the counter-based generator, smz_cartpole_step_ctl).  Without on_end and limit the step is the plain smz_cartpole_step /
+    smz_cartpole_step_pack."""
+    obs_dim, num_actions, _step_name = 4, 2, "smz_cartpole_step_ctl"
+    _zeroed = False
+
+    def _alloc_state(self):
+        self.state = torch.empty(self.B, 4, dtype=torch.float64, device=self.device)
+
+    def _state_ptrs(self):
+        return (_ptr(self.state),)
+
+    def _reset_seed(self):
+        return self.seed
 
     def reset(self):
         all_states = np.random.RandomState(self.seed).uniform(-0.05, 0.05, size=(self.total, 4))
         st = all_states[self.first_env:self.first_env + self.B]
         self.state.copy_(torch.from_numpy(np.ascontiguousarray(st)))
         self.obs.copy_(self.state.to(torch.float32))
-        self.terminated.zero_()
-        self.step_count.zero_()
-        self.episode.zero_()
-        if self.active is not None:
-            self.active.fill_(1)
+        self._reset_counters()
         return self.obs
 
     def reset_state_of(self, env, episode):
@@ -65,20 +122,6 @@ class CartPoleVec:
         out = (C.c_double * 4)()
         _lib.check(self.lib.smz_cartpole_reset_state(self.seed, int(env), int(episode), C.byref(out)))
         return np.array(list(out))
-
-    def _controlled(self):
-        return self.on_end != "continue" or self.limit > 0
-
-    def _ctl_struct(self):
-        if self._ctl is None:
-            P = lambda x: None if x is None else x.data_ptr()
-            self._ctl = _lib.EpisodeCtl(P(self.step_count), P(self.episode), P(self.active), self.limit, ON_END[self.on_end],
-                                        self.seed, self.first_env)
-        return self._ctl
-
-    def step(self, action):
-        """action: int32 [B] device tensor (index into action_map).  Asynchronous on the current stream."""
-        return self.step_and_record(action, None, 0, None, None, None)
 
     def fused_step(self, chunk_data, t):
         """The arguments of smz_search_mlp_act_cartpole for this env's next step (the step + record run in the tail of the
@@ -92,24 +135,20 @@ class CartPoleVec:
 
     def step_and_record(self, action, chunk_data, t, policy, child_visits, root_value):
         """step(action) + the trajectory record of this step (smz_traj_pack's layout) in one launch."""
-        s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        P = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        T = 0 if chunk_data is None else chunk_data.shape[0]
         if self._controlled():
-            _lib.check(self.lib.smz_cartpole_step_ctl(P(self.state), P(action), P(self.obs), P(self.reward), P(self.terminated),
-                                                      C.byref(self._ctl_struct()), P(chunk_data), T, int(t), P(policy),
-                                                      P(child_visits), P(root_value), self.B, s))
-        elif chunk_data is None:
+            return super().step_and_record(action, chunk_data, t, policy, child_visits, root_value)
+        P, s = _ptr, self._stream()
+        if chunk_data is None:
             _lib.check(self.lib.smz_cartpole_step(P(self.state), P(action), P(self.obs), P(self.reward), P(self.terminated),
                                                   self.B, s))
         else:
             _lib.check(self.lib.smz_cartpole_step_pack(P(self.state), P(action), P(self.obs), P(self.reward),
-                                                       P(self.terminated), P(chunk_data), T, int(t), P(policy),
+                                                       P(self.terminated), P(chunk_data), chunk_data.shape[0], int(t), P(policy),
                                                        P(child_visits), P(root_value), self.B, s))
         return self.obs, self.reward, self.terminated
 
 
-class Board2048Vec:
+class Board2048Vec(_DeviceEnvVec):
     """B games of 2048 stepped on the device: the built-in env WITH chance (a tile spawns after every move) and with illegal
     moves -- Stochastic MuZero's own single-player stochastic benchmark.  16 observations (exponent / 16), 4 actions (0 up,
     1 right, 2 down, 3 left), reward = the values of the tiles a move merges.  Rules, draws and the illegal-move rule:
@@ -120,36 +159,18 @@ class Board2048Vec:
     (no `fused_step`).  Env i (global index first_env + i) draws from game_seed = seed + first_env + i + 1000003 * episode, so
     a shard sees the rows of the single-GPU run.  `board` [B,16] uint8 exponents, `spawns` [B] int32 tiles spawned in the
     current game."""
-    obs_dim, num_actions = 16, 4
+    obs_dim, num_actions, _step_name = 16, 4, "smz_2048_step_ctl"
 
-    def __init__(self, num_envs, device, seed=0, first_env=0, total_envs=None, on_end="continue", limit=0):
-        self.lib = _lib.load()
-        self.B, self.device = int(num_envs), torch.device(device)
-        self.seed, self.first_env = int(seed), int(first_env)
-        self.total = int(total_envs) if total_envs is not None else self.first_env + self.B
-        assert on_end in ON_END
-        self.on_end, self.limit = on_end, int(limit)
+    def _alloc_state(self):
         self.board = torch.zeros(self.B, 16, dtype=torch.uint8, device=self.device)
         self.spawns = torch.zeros(self.B, dtype=torch.int32, device=self.device)
-        self.obs = torch.zeros(self.B, 16, dtype=torch.float32, device=self.device)
-        self.reward = torch.zeros(self.B, dtype=torch.float32, device=self.device)
-        self.terminated = torch.zeros(self.B, dtype=torch.uint8, device=self.device)     # the flag of the last step
-        self.step_count = torch.zeros(self.B, dtype=torch.int32, device=self.device)
-        self.episode = torch.zeros(self.B, dtype=torch.int32, device=self.device)
-        self.active = torch.ones(self.B, dtype=torch.uint8, device=self.device) if on_end == "mask" else None
-        self._ctl = None
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _state_ptrs(self):
+        return _ptr(self.board), _ptr(self.spawns)
 
     def reset(self):
-        self.terminated.zero_()
-        self.step_count.zero_()
-        self.episode.zero_()
-        if self.active is not None:
-            self.active.fill_(1)
-        P = lambda x: C.c_void_p(x.data_ptr())
-        _lib.check(self.lib.smz_2048_reset(P(self.board), P(self.spawns), P(self.obs), self.seed % (1 << 64), self.first_env,
+        self._reset_counters()
+        _lib.check(self.lib.smz_2048_reset(_ptr(self.board), _ptr(self.spawns), _ptr(self.obs), self._reset_seed(), self.first_env,
                                            None, self.B, self._stream()))
         return self.obs
 
@@ -159,28 +180,8 @@ class Board2048Vec:
         self.board.copy_(b)
         self.obs.copy_(self.board.to(torch.float32) * 0.0625)
 
-    def _ctl_struct(self):
-        if self._ctl is None:
-            P = lambda x: None if x is None else x.data_ptr()
-            self._ctl = _lib.EpisodeCtl(P(self.step_count), P(self.episode), P(self.active), self.limit, ON_END[self.on_end],
-                                        self.seed % (1 << 64), self.first_env)
-        return self._ctl
 
-    def step(self, action):
-        """action: int32 [B] device tensor.  Asynchronous on the current stream."""
-        return self.step_and_record(action, None, 0, None, None, None)
-
-    def step_and_record(self, action, chunk_data, t, policy, child_visits, root_value):
-        """step(action) + the trajectory record of this step (smz_traj_pack's layout, F = 31) in one launch."""
-        P = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        T = 0 if chunk_data is None else chunk_data.shape[0]
-        _lib.check(self.lib.smz_2048_step_ctl(P(self.board), P(self.spawns), P(action), P(self.obs), P(self.reward),
-                                              P(self.terminated), C.byref(self._ctl_struct()), P(chunk_data), T, int(t),
-                                              P(policy), P(child_visits), P(root_value), self.B, self._stream()))
-        return self.obs, self.reward, self.terminated
-
-
-class Connect4Vec:
+class Connect4Vec(_DeviceEnvVec):
     """B games of Connect Four stepped on the device: the built-in env with TWO players.  6 rows x 7 columns, 7 actions (drop a
     disc into column 0 .. 6), 43 observations (+1 a colour-0 disc, -1 a colour-1 disc, 0 empty, row-major from the bottom row;
     obs[42] = +1 when colour 0 is to move, else -1), reward +1 for the move that makes four in a row, 0 otherwise (a draw
@@ -195,35 +196,17 @@ class Connect4Vec:
     (no `fused_step`).  `seed`, `first_env` and `total_envs` are accepted for the common constructor shape: the game is
     deterministic, so a shard sees the rows of the single-GPU run whatever they are.  `discs` [B,2] uint64 as two int64 words:
     word p = the discs of colour p, bit 7 * c + r = column c, row r."""
-    obs_dim, num_actions = 43, 7
+    obs_dim, num_actions, _step_name = 43, 7, "smz_connect4_step_ctl"
 
-    def __init__(self, num_envs, device, seed=0, first_env=0, total_envs=None, on_end="continue", limit=0):
-        self.lib = _lib.load()
-        self.B, self.device = int(num_envs), torch.device(device)
-        self.seed, self.first_env = int(seed), int(first_env)
-        self.total = int(total_envs) if total_envs is not None else self.first_env + self.B
-        assert on_end in ON_END
-        self.on_end, self.limit = on_end, int(limit)
+    def _alloc_state(self):
         self.discs = torch.zeros(self.B, 2, dtype=torch.int64, device=self.device)      # (the bits of uint64 words; bit 63 unused)
-        self.obs = torch.zeros(self.B, 43, dtype=torch.float32, device=self.device)
-        self.reward = torch.zeros(self.B, dtype=torch.float32, device=self.device)
-        self.terminated = torch.zeros(self.B, dtype=torch.uint8, device=self.device)     # the flag of the last step
-        self.step_count = torch.zeros(self.B, dtype=torch.int32, device=self.device)
-        self.episode = torch.zeros(self.B, dtype=torch.int32, device=self.device)
-        self.active = torch.ones(self.B, dtype=torch.uint8, device=self.device) if on_end == "mask" else None
-        self._ctl = None
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _state_ptrs(self):
+        return (_ptr(self.discs),)
 
     def reset(self):
-        self.terminated.zero_()
-        self.step_count.zero_()
-        self.episode.zero_()
-        if self.active is not None:
-            self.active.fill_(1)
-        P = lambda x: C.c_void_p(x.data_ptr())
-        _lib.check(self.lib.smz_connect4_reset(P(self.discs), P(self.obs), self.B, self._stream()))
+        self._reset_counters()
+        _lib.check(self.lib.smz_connect4_reset(_ptr(self.discs), _ptr(self.obs), self.B, self._stream()))
         return self.obs
 
     def set_boards(self, discs):
@@ -231,26 +214,6 @@ class Connect4Vec:
         d = np.ascontiguousarray(discs, dtype=np.uint64).reshape(self.B, 2)
         self.discs.copy_(torch.from_numpy(d.view(np.int64)))
         self.obs.copy_(torch.from_numpy(_he.connect4_observations(d)))
-
-    def _ctl_struct(self):
-        if self._ctl is None:
-            P = lambda x: None if x is None else x.data_ptr()
-            self._ctl = _lib.EpisodeCtl(P(self.step_count), P(self.episode), P(self.active), self.limit, ON_END[self.on_end],
-                                        self.seed % (1 << 64), self.first_env)
-        return self._ctl
-
-    def step(self, action):
-        """action: int32 [B] device tensor.  Asynchronous on the current stream."""
-        return self.step_and_record(action, None, 0, None, None, None)
-
-    def step_and_record(self, action, chunk_data, t, policy, child_visits, root_value):
-        """step(action) + the trajectory record of this step (smz_traj_pack's layout, F = 67) in one launch."""
-        P = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        T = 0 if chunk_data is None else chunk_data.shape[0]
-        _lib.check(self.lib.smz_connect4_step_ctl(P(self.discs), P(action), P(self.obs), P(self.reward), P(self.terminated),
-                                                  C.byref(self._ctl_struct()), P(chunk_data), T, int(t), P(policy),
-                                                  P(child_visits), P(root_value), self.B, self._stream()))
-        return self.obs, self.reward, self.terminated
 
 
 class SyntheticVec:

@@ -26,6 +26,31 @@ def _binding():
     return lib
 
 
+def kernel_resources(tmp_path, source, game, reset_name):
+    """-> the resource metadata of (k_board_step_env<game>, the reset kernel), the unit's only two kernels, both without scratch
+    memory and spills."""
+    out = tmp_path / (source + ".s")
+    p = subprocess.run([HIPCC, *FLAGS, "-o", str(out), source], cwd=CSRC, stdout=subprocess.DEVNULL,
+                       stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    text = out.read_text()
+    meta = text[text.index("amdhsa.kernels:"):]
+    seen = {}
+    for k in re.split(r"\n  - ", meta)[1:]:
+        m = re.search(r"^    \.name:\s+(\S+)", k, re.M)
+        if m is None or ".private_segment_fixed_size" not in k:
+            continue
+        seen[m.group(1)] = {f: int(re.search(r"\.%s:\s+(\d+)" % f, k).group(1)) for f in FIELDS}
+    for n, f in sorted(seen.items()):
+        print(n, f)
+    step = [f for n, f in seen.items() if "k_board_step_env" in n and game in n]
+    reset = [f for n, f in seen.items() if reset_name in n]
+    assert len(step) == 1 and len(reset) == 1 and len(seen) == 2, sorted(seen)
+    for f in step + reset:
+        assert (f["private_segment_fixed_size"], f["vgpr_spill_count"], f["sgpr_spill_count"]) == (0, 0, 0), f
+    return step[0], reset[0]
+
+
 def test_header_binding_and_library_declare_the_entry_points():
     with open(os.path.join(ROOT, "include", "smz.h")) as f:
         h = f.read()
@@ -52,27 +77,9 @@ def test_header_binding_and_library_declare_the_entry_points():
 @pytest.mark.skipif(not os.path.exists(HIPCC) or os.environ.get("SMZ_SKIP_ISA_TESTS"),
                     reason="needs hipcc (cross-compiles without a GPU)")
 def test_the_step_kernel_has_no_scratch_and_the_stated_lds(tmp_path):
-    """k_connect4_step_env: no private segment (the position is two 64-bit registers and no array is indexed with a run-time
-    value), no spills, and 64 x 67 float64 record rows + 64 x 43 float32 observation rows of LDS = 45 312 bytes.  Reported, not
-    asserted: the register counts."""
-    out = tmp_path / "envconnect4.s"
-    p = subprocess.run([HIPCC, *FLAGS, "-o", str(out), "smz_envconnect4.hip"], cwd=CSRC, stdout=subprocess.DEVNULL,
-                       stderr=subprocess.PIPE, text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-2000:]
-    text = out.read_text()
-    meta = text[text.index("amdhsa.kernels:"):]
-    seen = {}
-    for k in re.split(r"\n  - ", meta)[1:]:
-        m = re.search(r"^    \.name:\s+(\S+)", k, re.M)
-        if m is None or ".private_segment_fixed_size" not in k:
-            continue
-        seen[m.group(1)] = {f: int(re.search(r"\.%s:\s+(\d+)" % f, k).group(1)) for f in FIELDS}
-    for n, f in sorted(seen.items()):
-        print(n, f)
-    step = [f for n, f in seen.items() if "k_connect4_step_env" in n]
-    reset = [f for n, f in seen.items() if "k_connect4_reset" in n]
-    assert len(step) == 1 and len(reset) == 1 and len(seen) == 2, sorted(seen)
-    for f in step + reset:
-        assert (f["private_segment_fixed_size"], f["vgpr_spill_count"], f["sgpr_spill_count"]) == (0, 0, 0), f
-    assert step[0]["group_segment_fixed_size"] == 64 * 67 * 8 + 64 * 43 * 4 == 45312
-    assert reset[0]["group_segment_fixed_size"] == 0
+    """k_board_step_env<GameConnect4>: no private segment (the position is two 64-bit registers and no array is indexed with a
+    run-time value), no spills, and 64 x 67 float64 record rows + 64 x 43 float32 observation rows of LDS = 45 312 bytes.
+    Reported, not asserted: the register counts."""
+    step, reset = kernel_resources(tmp_path, "smz_envconnect4.hip", "GameConnect4", "k_connect4_reset")
+    assert step["group_segment_fixed_size"] == 64 * 67 * 8 + 64 * 43 * 4 == 45312
+    assert reset["group_segment_fixed_size"] == 0

@@ -827,6 +827,60 @@ int smz_connect4_step_ctl(uint64_t *discs_dev, const int32_t *action_dev, float 
  * finished.  Outputs may be NULL. */
 int smz_connect4_host_step(uint64_t discs[2], int action, float *reward_out, int *terminated_out, int *illegal_out);
 
+/* ---- Othello (Reversi): a device-resident env with 65 actions and TWO players (csrc/smz_envothello.hip; the rules:
+ * csrc/smz_othello.hpp) --- */
+/* The built-in game for large-action handles (smz_create_large_actions).  Integer rules, so device, host and any restatement
+ * agree bit for bit.
+ *   board      8 rows x 8 columns.
+ *   state      discs [B][2] u64, 16 bytes per env, moved as one 128-bit access: discs_dev must be 16-byte aligned.  Word p holds
+ *              colour p's discs.  mover [B] i32: the colour to move (0 or 1); a pass changes it alone, so it cannot be read off
+ *              the board.
+ *   bit layout bit 8 * r + c is row r, column c; the same index is the observation index.
+ *   start      colour 0 on (3,4) and (4,3), colour 1 on (3,3) and (4,4), colour 0 to move.
+ *   actions    0 .. 63: place a disc of the mover on that square.  64: pass.
+ *   placement  legal when the square is empty and at least one of the 8 directions holds a contiguous run of opponent discs
+ *              ended by a disc of the mover; all such runs flip.  Then the other colour is to move.
+ *   pass       legal only when the mover has no legal placement and the opponent has one; it changes the mover, nothing else.
+ *   finished   neither colour has a legal placement (a full board and a wipe-out are cases of it).
+ *   illegal    an occupied square, a placement that flips nothing, a pass while a placement exists, an action outside 0 .. 64,
+ *              and any action on a finished position.
+ *   end        terminated when the position after a legal move is finished.
+ *   reward     0.0f for every move but the one that ends the game; that move gets +1.0f / -1.0f / 0.0f as the player who made
+ *              it has more / fewer / as many discs as the other.
+ *   obs        65 float32, exact.  obs[8 * r + c] is +1 for a colour-0 disc, -1 for a colour-1 disc, 0 when empty; obs[64] is
+ *              +1 when colour 0 is to move, else -1.  A pure function of the state.
+ *   reset      the start position.  The game is deterministic: the env makes no draws (ctl->reset_seed and ctl->first_env are
+ *              accepted for the common shape and unused).
+ * smz_othello_reset writes the start positions and, unless obs_out_dev is NULL, their observations. */
+int smz_othello_reset(uint64_t *discs_dev, int32_t *mover_dev, float *obs_out_dev, int B, smz_stream stream);
+/* One env step of every env in ONE launch (one lane per env, 64 lanes per workgroup of which the first 16 play an env each: a
+ * workgroup stages the rows of 16 envs in LDS): the move, the flips, the end test, the game bookkeeping of smz_episode_ctl and
+ * the trajectory record (smz_traj_pack's layout with obs_dim 65 and A 65: F = 263, the observations INSIDE the record; traj_dev
+ * may be NULL).  ctl is required, and so is ctl->step_count_dev.  The flag is smz_cartpole_step_ctl's: 0 running |
+ * 1 terminated | 2 stopped by ctl->limit | 3 no step (active_dev[e] == 0).  obs_out_dev gets the row of EVERY env,
+ * switched-off ones included (a pure function of the state).
+ * An ILLEGAL move follows the reference (game.py:123-131): position, mover and observation unchanged; reward
+ * min(-(steps so far), -limit, -1) with -limit = -inf when there is no limit; the move counter still advances; the terminated
+ * bit is whatever the current position says.  The search's root player is the move counter modulo the cycle, the colour to
+ * move comes from `mover`: after an illegal move the two disagree for the rest of that game (smz_connect4_step_ctl).
+ *   on_end 1: a finished env is switched off (active_dev[e] = 0).
+ *   on_end 2: the record keeps the finished position's observation; the env starts game episode + 1 from the start position
+ *             and the step count restarts (obs_out_dev shows the start position).
+ *   on_end 0: the env keeps stepping; a finished position then yields illegal-move records.
+ * SMZ_ERR_INVALID, returned before any HIP call: a null discs / mover / action / ctl / step_count pointer, B < 1, on_end 1
+ * without active_dev, on_end 2 without episode_dev, a trajectory without policy / child_visits / root_value or with t outside
+ * [0, T), a misaligned discs_dev. */
+int smz_othello_step_ctl(uint64_t *discs_dev, int32_t *mover_dev, const int32_t *action_dev, float *obs_out_dev,
+                         float *reward_out_dev, uint8_t *flag_out_dev, const smz_episode_ctl *ctl, double *traj_dev, int T, int t,
+                         const double *policy_dev, const double *child_visits_dev, const float *root_value_dev, int B,
+                         smz_stream stream);
+/* The same rule core compiled for the host, no GPU call: one game, one move.  An illegal move writes nothing and reports
+ * reward 0 (its penalty depends on the game's move count: the caller's).  terminated_out: the position as it is after the call
+ * is finished.  Outputs may be NULL; discs and mover may not. */
+int smz_othello_host_step(uint64_t discs[2], int *mover, int action, float *reward_out, int *terminated_out, int *illegal_out);
+/* The squares (bit 8 * r + c) on which `colour` (0 or 1) may place a disc in the position `discs`, whoever is to move. */
+int smz_othello_host_moves(const uint64_t discs[2], int colour, uint64_t *mask_out);
+
 /* Appends one env step of every tree to a fixed-length trajectory buffer laid out [T][B][F] (step-major, so one
  * step is one contiguous, coalesced slab and a finished chunk is one message for the trajectory gather):
  * what Game.policy_step / store_search_statistics append to their lists (game.py:193-195, 263-267).  Record of F =

@@ -83,7 +83,7 @@ def set_heads_backend(model, config):
 
 
 def make_env(name, num_envs, device, seed, limit=0, on_end="continue"):
-    """The vectorised environment of a run: the built-in device-resident CartPole, 2048 or Connect Four, or -- for any other name -- gymnasium
+    """The vectorised environment of a run: the built-in device-resident CartPole, 2048, Connect Four or Othello, or -- for any other name -- gymnasium
     environments stepped on the host behind the pinned-memory adapter (envs.HostVecEnv; needs gymnasium installed)."""
     from importlib import import_module
     envs = import_module("stochastic-muzero_amd.envs")
@@ -93,6 +93,8 @@ def make_env(name, num_envs, device, seed, limit=0, on_end="continue"):
         return envs.Board2048Vec(num_envs, device, seed=seed, on_end=on_end, limit=limit)
     if name.startswith(("Connect4", "ConnectFour")):
         return envs.Connect4Vec(num_envs, device, seed=seed, on_end=on_end, limit=limit)
+    if name.startswith(("Othello", "Reversi")):
+        return envs.OthelloVec(num_envs, device, seed=seed, on_end=on_end, limit=limit)
     try:
         import gymnasium as gym
     except ImportError:

@@ -149,6 +149,12 @@ SIGNATURES = {
     "smz_connect4_step_ctl": (C.c_int, [_P, _P, _P, _P, _P, C.POINTER(EpisodeCtl), _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P]),
     "smz_connect4_host_step": (C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int),
                                          C.POINTER(C.c_int)]),
+    "smz_othello_reset": (C.c_int, [_P, _P, _P, C.c_int, _P]),
+    "smz_othello_step_ctl": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(EpisodeCtl), _P, C.c_int, C.c_int, _P, _P, _P, C.c_int,
+                                       _P]),
+    "smz_othello_host_step": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float),
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "smz_othello_host_moves": (C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_uint64)]),
     "smz_set_active": (C.c_int, [_P, _P]),
     "smz_set_players": (C.c_int, [_P, C.c_int, _P, _P]),
     "smz_set_leaf_ids_out": (C.c_int, [_P, _P]),

@@ -1,4 +1,4 @@
-// smz_env_frame.hpp -- what the device-resident board games share (smz_env2048.hip, smz_envconnect4.hip): the game bookkeeping
+// smz_env_frame.hpp -- what the device-resident board games share (smz_env2048.hip, smz_envconnect4.hip, smz_envothello.hip): the game bookkeeping
 // of smz_episode_ctl (limit, mask / restart at a game's end, the reference's illegal-move rule, game.py:123-131), the trajectory
 // record, the step kernel and the argument checks of the *_step_ctl entry points.  A game brings its rules as a traits struct:
 //
@@ -14,6 +14,9 @@
 //       template <typename T> static void write_obs(T *row, const State &);                 // kObs values, float or double
 //       static constexpr bool kStageObs;               // the observation rows go out through LDS (put_obs); false: the game
 //       static void write_obs_direct(float *row, const State &);                            // ... stores its row in global memory
+//       static constexpr int kEnvs;                    // OPTIONAL: the envs one 64-lane workgroup plays, a divisor of 64 (64
+//                                                      // when absent).  A game with wide rows states fewer, so that its rows
+//                                                      // fit LDS several workgroups to a compute unit (smz_envothello.hip)
 //   };
 //
 // seed, env (the global index) and episode name the game for the draws of a game with chance; a game without ignores them.
@@ -103,26 +106,40 @@ __device__ inline void env_step_lane(const Game &G, const EnvFrame &E, int e, co
     put_obs<Game>(E, e, o, s, legal || restart);
 }
 
+// The envs of one workgroup: Game::kEnvs where the game states it, else one per lane.
+template <class Game, class = void>
+struct EnvsPerGroup {
+    static constexpr int value = 64;
+};
+template <class Game>
+struct EnvsPerGroup<Game, decltype((void)Game::kEnvs)> {
+    static constexpr int value = Game::kEnvs;
+};
+
 // One lane per env, one wavefront per workgroup (4096 envs: 64 workgroups, so the launch spreads over 64 compute units; the
 // step is a short chain of dependent loads and integer arithmetic, latency not throughput).  The record rows (kF float64) and,
 // with kStageObs, the observation rows (kObs float32) of a workgroup's envs are one contiguous run each, built in LDS and
 // written out with coalesced stores: 64 x 8 kF bytes = 15.5 KB for 2048, 64 x (4 kObs + 8 kF) = 44.25 KB for Connect Four.  A
 // lane writing its own rows would touch cache lines that its neighbours touch again.  The policy and child-visit rows come in
 // the same way: [n][kA] float64 is contiguous per workgroup, read coalesced and scattered into the LDS rows.
+// A game with kEnvs < 64 has lanes < kEnvs play; all 64 lanes move the runs, and LDS holds kEnvs rows (Othello: 16 x 2364 bytes
+// = 36.9 KB and 256 workgroups for 4096 envs; with 64 envs per workgroup its 147.75 KB leave one workgroup to a compute unit and
+// the launch takes twice as long, profiles/r22_othello_rate.txt).
 constexpr int kStepThreads = 64;
 template <class Game>
 __global__ void __launch_bounds__(kStepThreads) k_board_step_env(Game G, EnvFrame E, const int32_t *action, int B,
                                                                  const double *policy, const double *child_visits,
                                                                  const float *root_value) {
-    constexpr int kObs = Game::kObs, kA = Game::kA, kF = kObs + 3 * kA + 3;
-    __shared__ double rows[kStepThreads * kF];
+    constexpr int kObs = Game::kObs, kA = Game::kA, kF = kObs + 3 * kA + 3, kEnvs = EnvsPerGroup<Game>::value;
+    static_assert(kEnvs >= 1 && kEnvs <= kStepThreads && kStepThreads % kEnvs == 0, "kEnvs divides the workgroup");
+    __shared__ double rows[kEnvs * kF];
     float *obs_rows = nullptr;
     if constexpr (Game::kStageObs) {
-        __shared__ float staged[kStepThreads * kObs];
+        __shared__ float staged[kEnvs * kObs];
         obs_rows = staged;
     }
-    const int lane = (int)threadIdx.x, e0 = blockIdx.x * kStepThreads, e = e0 + lane;
-    const int n = B - e0 < kStepThreads ? B - e0 : kStepThreads;         // envs of this workgroup (>= 1 by the grid)
+    const int lane = (int)threadIdx.x, e0 = blockIdx.x * kEnvs, e = e0 + lane;
+    const int n = B - e0 < kEnvs ? B - e0 : kEnvs;                       // envs of this workgroup (>= 1 by the grid)
     const bool record = E.traj != nullptr;                               // (the same for every lane)
     if (record) {
         const double *p = policy + (size_t)e0 * kA, *v = child_visits + (size_t)e0 * kA;
@@ -133,7 +150,7 @@ __global__ void __launch_bounds__(kStepThreads) k_board_step_env(Game G, EnvFram
         }
         __syncthreads();                         // a switched-off env zeroes its whole row
     }
-    if (e < B) env_step_lane(G, E, e, action, root_value, record ? rows + lane * kF : nullptr,
+    if (kEnvs == kStepThreads ? e < B : lane < n) env_step_lane(G, E, e, action, root_value, record ? rows + lane * kF : nullptr,
                                Game::kStageObs ? obs_rows + lane * kObs : nullptr);
     __syncthreads();
     if (Game::kStageObs && E.obs_out) {
@@ -166,7 +183,8 @@ int launch_board_step(const Game &G, const int32_t *action_dev, float *obs_out_d
                       const double *child_visits_dev, const float *root_value_dev, int B, smz_stream stream) {
     const EnvFrame E = {obs_out_dev, reward_out_dev, flag_out_dev, ctl->step_count_dev, ctl->episode_dev, ctl->active_dev,
                         ctl->limit, ctl->on_end, (uint64_t)ctl->reset_seed, (long long)ctl->first_env, traj_dev, t};
-    hipLaunchKernelGGL(k_board_step_env<Game>, dim3((unsigned)((B + kStepThreads - 1) / kStepThreads)), dim3(kStepThreads), 0,
+    constexpr int kEnvs = EnvsPerGroup<Game>::value;
+    hipLaunchKernelGGL(k_board_step_env<Game>, dim3((unsigned)((B + kEnvs - 1) / kEnvs)), dim3(kStepThreads), 0,
                        (hipStream_t)stream, G, E, action_dev, B, policy_dev, child_visits_dev, root_value_dev);
     return launch_check();
 }

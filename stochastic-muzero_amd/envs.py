@@ -2,7 +2,8 @@
 
 gymnasium is not part of this image, so the environments here are this engine's own: a CartPole-v1 shaped Euler
 integrator (float64 state, float32 observations; physics constants as published for CartPole-v1), the game 2048 (chance
-tile spawns, illegal moves: Board2048Vec), the two-player game Connect Four (Connect4Vec) and a LunarLander-shaped stand-in that only provides observations of the right width.  Env i of a job draws its initial
+tile spawns, illegal moves: Board2048Vec), the two-player game Connect Four (Connect4Vec), the 65-action two-player game Othello
+(OthelloVec) and a LunarLander-shaped stand-in that only provides observations of the right width.  Env i of a job draws its initial
 state from `RandomState(seed).uniform(...)[i]`, so a shard sees exactly the rows it would see in a single-GPU run.
 """
 import ctypes as C
@@ -216,6 +217,48 @@ class Connect4Vec(_DeviceEnvVec):
         self.obs.copy_(torch.from_numpy(_he.connect4_observations(d)))
 
 
+class OthelloVec(_DeviceEnvVec):
+    """B games of Othello (Reversi) stepped on the device: the built-in env with MORE THAN 32 actions, so the game of the
+    large-action handles (smz_create_large_actions, the large-action and broad heads).  8 x 8 squares, two players, 65 actions
+    (0 .. 63 place a disc of the mover on square 8 * r + c, 64 passes), 65 observations (+1 a colour-0 disc, -1 a colour-1
+    disc, 0 empty; obs[64] = +1 when colour 0 is to move, else -1).  Reward 0 but for the move that ends the game: +1 / -1 / 0 as
+    the player who made it has more / fewer / as many discs.  An occupied square, a placement that flips nothing, a pass while
+    a placement exists, an action outside 0 .. 64 and any action on a finished position are illegal, under the reference's
+    rule.  Rules and bit layout: include/smz.h (smz_othello_step_ctl), DESIGN.md section 8.4.  Integer rules and no draws:
+    host_envs.HostOthello under HostVecEnv plays the very same games.
+
+    The colour to move is part of the state (`mover`: a pass changes it alone); a multi-player search takes its root player
+    from `step_count` (selfplay), and the two agree until a game's first illegal move.
+
+    The attributes and methods of Connect4Vec (on_end / limit, `seed` / `first_env` / `total_envs` accepted and unused); the
+    step is a launch of its own behind the search (no `fused_step`).  Its record holds the 65 observations (`rec_obs_dim`:
+    selfplay.chunk_for), F = 263.  `discs` [B,2] uint64 as two int64 words: word p = the discs of colour p, bit 8 * r + c = row
+    r, column c; `mover` [B] int32."""
+    obs_dim, num_actions, _step_name = 65, 65, "smz_othello_step_ctl"
+    rec_obs_dim = 65                             # the step launch writes the observations into the record
+    envs_per_group = 16                          # GameOthello::kEnvs (csrc/smz_envothello.hip): envs of one workgroup
+
+    def _alloc_state(self):
+        self.discs = torch.zeros(self.B, 2, dtype=torch.int64, device=self.device)      # (the bits of uint64 words)
+        self.mover = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+
+    def _state_ptrs(self):
+        return _ptr(self.discs), _ptr(self.mover)
+
+    def reset(self):
+        self._reset_counters()
+        _lib.check(self.lib.smz_othello_reset(_ptr(self.discs), _ptr(self.mover), _ptr(self.obs), self.B, self._stream()))
+        return self.obs
+
+    def set_boards(self, discs, mover):
+        """Replaces the positions (tests): [B,2] uint64 words and [B] colours to move.  The counters go on from where they are."""
+        d = np.ascontiguousarray(discs, dtype=np.uint64).reshape(self.B, 2)
+        m = np.ascontiguousarray(mover, dtype=np.int32).reshape(self.B)
+        self.discs.copy_(torch.from_numpy(d.view(np.int64)))
+        self.mover.copy_(torch.from_numpy(m))
+        self.obs.copy_(torch.from_numpy(_he.othello_observations(d, m)))
+
+
 class SyntheticVec:
     """Observation-only stand-in (e.g. LunarLander-shaped: obs 8 ~ N(0,1), 4 actions; Box2D is absent here).  The
     observations are generated on the device (smz_synthetic_obs): element (env, k) of step t is a pure function of
@@ -283,7 +326,7 @@ class ImageVec:
         return self.obs, self.reward, self.terminated
 
 
-from .host_envs import HostCartPole, HostCartPoleRender, Host2048, Board2048Batch, HostConnect4, Connect4Batch  # noqa: E402,F401  (numpy-only module: the worker processes import it too)
+from .host_envs import HostCartPole, HostCartPoleRender, Host2048, Board2048Batch, HostConnect4, Connect4Batch, HostOthello, OthelloBatch  # noqa: E402,F401  (numpy-only module: the worker processes import it too)
 from . import host_envs as _he  # noqa: E402
 
 

@@ -505,6 +505,161 @@ class Connect4Batch:
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# Othello on the host: the rules of csrc/smz_othello.hpp, restated (include/smz.h)
+# ---------------------------------------------------------------------------------------------------------------------------
+_OTH_ALL = 0xFFFFFFFFFFFFFFFF
+_OTH_INNER = 0x7E7E7E7E7E7E7E7E                              # the files b .. g: no run passes through the a- or the h-file
+_OTH_DIRS = tuple((s, _OTH_ALL if abs(s) == 8 else _OTH_INNER) for s in (1, -1, 8, -8, 9, -9, 7, -7))
+_OTH_START = (1 << 28 | 1 << 35, 1 << 27 | 1 << 36)          # colour 0 on (3,4) and (4,3), colour 1 on (3,3) and (4,4)
+_OTH_SHIFTS = np.arange(64, dtype=np.uint64)
+
+
+def _oth_shift(x, s):
+    """One step in direction s (bits) of a Python integer or a uint64 array; what leaves the 64 bits is gone."""
+    if isinstance(x, np.ndarray):
+        return x << np.uint64(s) if s > 0 else x >> np.uint64(-s)
+    return (x << s) & _OTH_ALL if s > 0 else x >> -s
+
+
+def _oth_run(start, opp, s, mask):
+    """The run of opponent discs next to `start` in direction s: one seed step and five fills (a run holds at most 6 discs)."""
+    m = opp & (np.uint64(mask) if isinstance(opp, np.ndarray) else mask)
+    t = m & _oth_shift(start, s)
+    for _ in range(5):
+        t = t | (m & _oth_shift(t, s))
+    return t
+
+
+def _oth_moves(me, opp):
+    """The squares on which the colour with discs `me` may place a disc (Python integers, or uint64 arrays)."""
+    moves = me & 0
+    for s, mask in _OTH_DIRS:
+        moves = moves | _oth_shift(_oth_run(me, opp, s, mask), s)
+    return moves & ~(me | opp) & (np.uint64(_OTH_ALL) if isinstance(me, np.ndarray) else _OTH_ALL)
+
+
+def _oth_flips(x, me, opp):
+    """The opponent discs a disc placed on `x` (one bit; an array may hold 0: no flips) turns."""
+    flips = me & 0
+    for s, mask in _OTH_DIRS:
+        t = _oth_run(x, opp, s, mask)
+        closed = (_oth_shift(t, s) & me) != 0
+        flips = flips | (np.where(closed, t, np.uint64(0)) if isinstance(me, np.ndarray) else (t if closed else 0))
+    return flips
+
+
+def othello_observations(discs, mover):
+    """[n][2] uint64 positions and [n] colours to move -> [n][65] float32 observations: obs[8 * r + c] = +1 / -1 / 0 for a
+    colour-0 disc, a colour-1 disc, an empty square; obs[64] = +1 when colour 0 is to move, else -1."""
+    d = np.asarray(discs, np.uint64).reshape(-1, 2)
+    obs = np.empty((len(d), 65), np.float32)
+    one = np.uint64(1)
+    obs[:, :64] = ((d[:, :1] >> _OTH_SHIFTS) & one).astype(np.float32) - ((d[:, 1:] >> _OTH_SHIFTS) & one).astype(np.float32)
+    obs[:, 64] = np.where(np.asarray(mover).reshape(-1) != 0, -1.0, 1.0)
+    return obs
+
+
+class HostOthello:
+    """One game of Othello on the host behind the gym call shape: the game envs.OthelloVec plays on the device, rule for rule.
+    65 actions: 0 .. 63 place a disc of the mover on square 8 * r + c, 64 passes.  The game is deterministic: reset(seed=)
+    ignores the seed.  An illegal move -- an occupied square, a placement that flips nothing, a pass while a placement exists,
+    an action outside 0 .. 64, any move on a finished position -- raises ValueError and changes nothing.
+    discs: 2 uint64 words, word p = the discs of colour p, bit 8 * r + c = row r, column c; mover: 1 int32, the colour to move."""
+
+    def __init__(self):
+        self.discs = np.zeros(2, np.uint64)
+        self.mover = np.zeros(1, np.int32)
+        self.reset()
+
+    def _observation(self):
+        return othello_observations(self.discs, self.mover)[0]
+
+    def legal_moves(self, colour=None):
+        """The placement squares of `colour` (default: the mover) as a 64-bit mask."""
+        c = int(self.mover[0]) if colour is None else int(colour)
+        return _oth_moves(int(self.discs[c]), int(self.discs[1 - c]))
+
+    def reset(self, seed=None):
+        self.discs[:] = _OTH_START                          # (in place: a batch stepper may own the rows)
+        self.mover[:] = 0
+        return self._observation(), {}
+
+    def step(self, action):
+        if not isinstance(action, (int, np.integer)) or not 0 <= int(action) <= 64:
+            raise ValueError(f"illegal action {action!r}")
+        action, c = int(action), int(self.mover[0])
+        me, opp = int(self.discs[c]), int(self.discs[1 - c])
+        mine = _oth_moves(me, opp)
+        if not mine and not _oth_moves(opp, me):
+            raise ValueError(f"illegal move {action!r}: the game is over")
+        if action == 64:
+            if mine:
+                raise ValueError("illegal pass: a placement exists")
+            self.mover[0] = 1 - c
+            return self._observation(), 0.0, False, False, {}
+        x = 1 << action
+        if not x & mine:
+            raise ValueError(f"illegal move {action!r}: " + ("the square is occupied" if x & (me | opp) else "it flips nothing"))
+        f = _oth_flips(x, me, opp)
+        me, opp = me | x | f, opp & ~f
+        self.discs[c], self.discs[1 - c] = me, opp
+        self.mover[0] = 1 - c
+        over = not _oth_moves(opp, me) and not _oth_moves(me, opp)          # (the new mover's placements first: mostly some)
+        a, b = bin(me).count("1"), bin(opp).count("1")
+        return self._observation(), float((a > b) - (a < b)) if over else 0.0, over, False, {}
+
+    def close(self):
+        pass
+
+    @classmethod
+    def make_batch(cls, envs):
+        return OthelloBatch(envs)
+
+
+class OthelloBatch:
+    """HostOthello.step for a whole slice at once (the make_batch / reset_one / step_batch protocol of CartPoleBatch): the
+    positions of the slice's n envs are ONE [n][2] uint64 array and the movers ONE [n] int32 array (every env object's `discs`
+    and `mover` become views of them) and a step is a fixed number of numpy operations on uint64 arrays.  Same rules: the
+    per-env class is the checker (tests/test_envothello.py)."""
+
+    def __init__(self, envs):
+        self.envs = list(envs)
+        n = len(self.envs)
+        self.discs = np.zeros((n, 2), np.uint64)
+        self.mover = np.zeros(n, np.int32)
+        for i, e in enumerate(self.envs):
+            self.discs[i], self.mover[i] = e.discs, e.mover[0]
+            e.discs, e.mover = self.discs[i], self.mover[i:i + 1]                  # views
+
+    def reset_one(self, i, seed):
+        obs, _ = self.envs[i].reset(seed=seed)              # (writes through the views)
+        return obs
+
+    def step_batch(self, actions, go):
+        actions, go = np.asarray(actions, np.int64), np.asarray(go, bool)
+        d, zero = self.discs, np.uint64(0)
+        second = self.mover != 0
+        me, opp = np.where(second, d[:, 1], d[:, 0]), np.where(second, d[:, 0], d[:, 1])
+        mine, theirs = _oth_moves(me, opp), _oth_moves(opp, me)
+        finished = (mine | theirs) == 0
+        square = (actions >= 0) & (actions < 64)
+        x = np.where(square, np.uint64(1) << np.where(square, actions, 0).astype(np.uint64), zero)
+        placed = go & ~finished & ((x & mine) != 0)
+        passed = go & ~finished & (actions == 64) & (mine == 0)
+        illegal = go & ~placed & ~passed
+        x = np.where(placed, x, zero)
+        f = _oth_flips(x, me, opp)
+        me, opp = me | x | f, opp & ~f
+        d[:, 0], d[:, 1] = np.where(second, opp, me), np.where(second, me, opp)
+        self.mover[placed | passed] ^= 1
+        over = placed & ((_oth_moves(me, opp) | _oth_moves(opp, me)) == 0)
+        a, b = _c4_popcount(me), _c4_popcount(opp)
+        reward = np.where(over, np.sign(a - b), 0).astype(np.float64)
+        term = np.where(placed | passed, over, finished)
+        return othello_observations(d, self.mover), reward, term, illegal
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # observation adapters: what of env.reset / env.step's observation goes into the env's row
 # ---------------------------------------------------------------------------------------------------------------------------
 def tap_index(n_in, n_out):

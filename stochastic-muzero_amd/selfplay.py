@@ -53,12 +53,16 @@ class TrajectoryChunk:
     Image observations (obs_dim > SPLIT_OBS: a 98x98x3 frame is 28 812 floats) are NOT widened into the float64 record: they
     are kept as float32 -- what the heads consume and what the reference's Game stores (game.py:264) -- in `obs`
     [T][B][obs_dim], and the record carries the other fields only (`rec_obs_dim` = 0).  Vector observations stay inside the
-    record (`obs` is None, `rec_obs_dim` = obs_dim)."""
+    record (`obs` is None, `rec_obs_dim` = obs_dim).  `rec_obs_dim` (0 or obs_dim) overrides the rule: a built-in env whose
+    step launch writes its own record states where its observations go (envs.OthelloVec: 65 observations, inside the record)."""
     SPLIT_OBS = 64
 
-    def __init__(self, T, B, obs_dim, A, device):
+    def __init__(self, T, B, obs_dim, A, device, rec_obs_dim=None):
         self.T, self.B, self.obs_dim, self.A = int(T), int(B), int(obs_dim), int(A)
-        self.rec_obs_dim = 0 if self.obs_dim > self.SPLIT_OBS else self.obs_dim
+        if rec_obs_dim is None:
+            rec_obs_dim = 0 if self.obs_dim > self.SPLIT_OBS else self.obs_dim
+        assert int(rec_obs_dim) in (0, self.obs_dim), rec_obs_dim
+        self.rec_obs_dim = int(rec_obs_dim)
         self.F = _lib.load().smz_traj_floats(self.rec_obs_dim, self.A)
         self.data = torch.zeros(self.T, self.B, self.F, dtype=torch.float64, device=device)
         self.obs = None if self.rec_obs_dim else torch.zeros(self.T, self.B, self.obs_dim, dtype=torch.float32, device=device)
@@ -104,6 +108,11 @@ class TrajectoryChunk:
                     policy=d[..., o + 2:o + 2 + A],
                     action_onehot=d[..., o + 2 + A:o + 2 + 2 * A], root_value=d[..., o + 2 + 2 * A],
                     child_visits=d[..., o + 3 + 2 * A:o + 3 + 3 * A])
+
+
+def chunk_for(env, T):
+    """The TrajectoryChunk of T steps of `env`: its observations go where the env says (`env.rec_obs_dim`), else by width."""
+    return TrajectoryChunk(T, env.B, env.obs_dim, env.num_actions, env.device, rec_obs_dim=getattr(env, "rec_obs_dim", None))
 
 
 _POWERS = {}
@@ -478,7 +487,7 @@ def play_games(env, heads, mcts, temperature, steps, chunk=None, train=True, t0=
     """Plays `steps` env steps of all env.B environments into rows [t0, t0 + steps) of the TrajectoryChunk (device resident)
     and returns it.  Everything is enqueued asynchronously on the current stream; the caller synchronises."""
     if chunk is None:
-        chunk = TrajectoryChunk(t0 + steps, env.B, env.obs_dim, env.num_actions, env.device)
+        chunk = chunk_for(env, t0 + steps)
     assert chunk.T >= t0 + steps and chunk.B == env.B
     _sync_active(env, mcts)
     for t in range(t0, t0 + steps):
@@ -500,7 +509,7 @@ class StreamGroup:
     def __init__(self, env, heads, mcts, steps, stream=None):
         self.env, self.heads, self.mcts = env, heads, mcts
         self.stream = stream if stream is not None else torch.cuda.Stream(device=env.device)
-        self.chunk = TrajectoryChunk(steps, env.B, env.obs_dim, env.num_actions, env.device)
+        self.chunk = chunk_for(env, steps)
 
 
 def play_games_grouped(groups, temperature, steps, train=True, t0=0):
@@ -735,7 +744,7 @@ def _play_and_gather(env, heads, mcts, temperature, steps, gather):
         # stream while the next slice is searched; only the last slice's transfer is exposed
         n = max(1, min(gather.slices, steps))
         cuts = [steps * k // n for k in range(n + 1)]
-        chunk = TrajectoryChunk(steps, env.B, env.obs_dim, env.num_actions, env.device)
+        chunk = chunk_for(env, steps)
         for k in range(n):
             play_games(env, heads, mcts, temperature, cuts[k + 1] - cuts[k], chunk=chunk, t0=cuts[k])
             gather.start(chunk.data[cuts[k]:cuts[k + 1]], None if chunk.obs is None else chunk.obs[cuts[k]:cuts[k + 1]])

@@ -1,8 +1,10 @@
 """What a device-resident board game costs and what it buys: envs.Board2048Vec against host_envs.Host2048 (--game 2048), or
-envs.Connect4Vec against host_envs.HostConnect4 under the two-player search (--game connect4), the host envs behind HostVecEnv.
+envs.Connect4Vec against host_envs.HostConnect4 under the two-player search (--game connect4), or envs.OthelloVec against
+host_envs.HostOthello under the two-player search on a large-action handle (--game othello), the host envs behind HostVecEnv.
 
 Everything at `--envs` environments (4096), one GPU:
-  step      the env step launch alone (smz_2048_step_ctl / smz_connect4_step_ctl with its trajectory record, on_end "reset"):
+  step      the env step launch alone (smz_2048_step_ctl / smz_connect4_step_ctl / smz_othello_step_ctl with its trajectory
+            record, on_end "reset"):
             `--steps` launches back to back on one stream between two device events, uploaded random actions; three blocks, the
             median is reported.  That figure is the rate at which this process can issue the launch (the host's enqueue
             included), not a kernel time; the kernel time comes from the profiler, in a run of its own:
@@ -10,7 +12,7 @@ Everything at `--envs` environments (4096), one GPU:
   selfplay  simulations/s of self-play (selfplay.play_games: search + action + env step + record per env step) with a fresh
             mlp_model that fits LDS (the game's obs and A, S 31, H 64, L 0: for 2048 the checkpoint-421 widths), `--sims`
             simulations (50), on_end "reset": on the device env, and on HostVecEnv([host env] * envs, workers=W) for every W of
-            --workers (2048: 0,8,14; connect4: 0,8).  One warm-up chunk, then five blocks of `--chunks` chunks of `--chunk` env
+            --workers (2048: 0,8,14; connect4 and othello: 0,8).  One warm-up chunk, then five blocks of `--chunks` chunks of `--chunk` env
             steps, each block between synchronisations (16 x 32 steps: a fifth of a second or more); the median block is
             reported, min and max printed.
             connect4 plays with number_of_player = 2 and limit 42, once for each search of --searches (stepwise: the step-wise
@@ -18,9 +20,11 @@ Everything at `--envs` environments (4096), one GPU:
             processes, and the two-player search takes its root player from them: the tool keeps a device copy for those cells
             (one in-place tensor update per env step, from the uploaded flags: under on_end "reset" the counter restarts
             whenever the flag is non-zero).
+            othello plays with number_of_player = 2 and limit 120 on a large-action handle (65 actions), step-wise only: the
+            large-action single launch (smz_search_mlp_large) is one player only, so --searches is "stepwise" for this game.
 Prints one JSON line per measurement and, with --out, appends the same lines to a file.
 
-    python tools/env_rate.py --game 2048|connect4 [--envs 4096] [--sims 50] [--workers 0,8] [--searches stepwise,single]
+    python tools/env_rate.py --game 2048|connect4|othello [--envs 4096] [--sims 50] [--workers 0,8] [--searches stepwise,single]
                              [--only step|selfplay] [--out FILE]
 """
 import argparse
@@ -36,9 +40,12 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-# device class, host class, obs, A, limit of the self-play games, players, default --workers
+# device class, host class, obs, A, limit of the self-play games, players, default --workers, default --searches
 GAMES = {"2048": dict(dev="Board2048Vec", host="Host2048", obs=16, A=4, limit=0, players=1, workers="0,8,14"),
-         "connect4": dict(dev="Connect4Vec", host="HostConnect4", obs=43, A=7, limit=42, players=2, workers="0,8")}
+         "connect4": dict(dev="Connect4Vec", host="HostConnect4", obs=43, A=7, limit=42, players=2, workers="0,8",
+                          searches="stepwise,single"),
+         "othello": dict(dev="OthelloVec", host="HostOthello", obs=65, A=65, limit=120, players=2, workers="0,8",
+                         searches="stepwise")}
 
 
 def main():
@@ -51,7 +58,8 @@ def main():
     ap.add_argument("--chunks", type=int, default=16)
     ap.add_argument("--only", choices=("step", "selfplay"), default=None)
     ap.add_argument("--workers", default=None)
-    ap.add_argument("--searches", default="stepwise,single", help="connect4 only")
+    ap.add_argument("--searches", default=None, help="two-player games: stepwise,single (connect4); stepwise (othello: the "
+                    "large-action single launch is one player only)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "a rate is measured on the GPU or not at all"
@@ -60,6 +68,9 @@ def main():
     game, dev, B = GAMES[a.game], "cuda:0", a.envs
     if a.workers is None:
         a.workers = game["workers"]
+    if a.searches is None:
+        a.searches = game.get("searches", "")
+    assert a.game != "othello" or a.searches == "stepwise", "a two-player search on a large-action handle is step-wise"
     name = torch.cuda.get_device_name(0)
 
     def emit(**rec):

@@ -11,6 +11,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
+MAX_A = 1024       # ORC_MAX_A of smz_oracle.c (= the engine's SMZ_MAX_ACTIONS_LARGE)
 
 
 def build(force=False):
@@ -134,6 +135,8 @@ class Tree:
         self._pbc = np.ascontiguousarray(pbc, dtype=np.float64)
         assert self._pbc.size >= cfg.sims + 2
         self.h = self.L.orc_tree_new(C.byref(cfg), _p(self._pbc))
+        if not self.h:
+            raise ValueError(f"the oracle takes 1 .. {MAX_A} actions and sampled children, not A = {cfg.A}, K = {cfg.K}")
         self.N = 1 + cfg.A + cfg.sims * cfg.K
 
     def __del__(self):

@@ -1,7 +1,7 @@
 """Large-action handles (smz_create_large_actions: one wavefront per tree, up to 1024 actions) on the GPU.  Every comparison is
 exact: the wave-per-tree kernels must reproduce the per-lane kernels on every tree they share (A <= 32) and the oracle
-(oracle/smz_oracle.c, numpy's arithmetic restated) above that, up to the oracle's 128 actions; above 128 numpy itself pins the
-pairwise sums."""
+(oracle/smz_oracle.c, numpy's arithmetic restated, 1 .. 1024 actions) above that: here up to 128 actions, in
+test_gpu_large_actions_oracle.py from 129 to 1024.  The tests of wider roots in this file check numpy's pairwise sums directly."""
 import glob
 import os
 
@@ -160,7 +160,7 @@ def test_large_action_handle_equals_the_oracle(A, K):
 
 @pytest.mark.parametrize("A,K", [(256, 2), (256, 256), (1000, 2), (1024, 3)])
 def test_wide_roots_follow_numpys_pairwise_sums(A, K):
-    """Above the oracle's 128 actions: the root priors are numpy's (policy + 1e-12) / sum with numpy's pairwise float32 sum,
+    """Above numpy's 128-element summation block, against numpy itself: the root priors are numpy's (policy + 1e-12) / sum with numpy's pairwise float32 sum,
     the visit-policy of act is numpy's, every simulation adds one visit, graph-free and fused runs agree."""
     B, S, sims = 64, 8, 12
     root, steps = _heads_tape(B, A, S, sims, seed=A + 3 * K)
@@ -313,7 +313,7 @@ def _check_acts(eng, data, sims):
 @pytest.mark.parametrize("fused", [False, True])
 @pytest.mark.parametrize("name", LARGE)
 def test_reference_fixtures_above_32_actions(name, fused):
-    """The reference's own searches with 33 .. 1000 actions (tools/gen_golden_large_actions.py): trees, device-drawn Dirichlet
+    """The reference's own searches with 33 .. 1024 actions (tools/gen_golden_large_actions.py): trees, device-drawn Dirichlet
     priors (float64, exact), paths, MinMax, stream positions, and the act outputs at every temperature."""
     import gpu_harness as gh
     eng, cfg, data = drive(name, fused=fused)

@@ -1,9 +1,9 @@
 """Step-wise searches whose recurrent networks are the large-action HIP heads (heads.HipMlpLargeHeads, Muzero.heads(backend=
 "large")): a round is three launches -- select, smz_mlp_recurrent_large, expand + backup -- on a large-action handle.
 
-What stands in for the trees' reference.  oracle/smz_oracle.c holds at most 128 actions (ORC_MAX_A sizes its stack arrays) and
-knows one player, so:
-  * the bit-for-bit replay against orc.Tree runs at A = 128, the oracle's limit (K = 3, 20 simulations, 8 trees);
+What stands in for the trees' reference.  oracle/smz_oracle.c knows one player, so:
+  * the bit-for-bit replay against orc.Tree runs at A = 128 (K = 3, 20 simulations, 8 trees; the same chain at 129 and 1024
+    actions, with the whole-search kernel at its end, is in tests/test_gpu_large_actions_oracle.py);
   * at A = 256, and with two players at A = 64, the recorded head outputs of every round are replayed as a tape on a second
     engine, which must build the same trees bit for bit (expand consumed exactly what the heads wrote, in the rows select
     named), and every round's head outputs must be the float64 restatement's on that round's parent rows, actions and

@@ -57,21 +57,23 @@ def test_header_library_and_binding_declare_the_large_action_entry_point():
     assert "smz_create_large_actions" in lib.SIGNATURES
 
 
-def _large_fixtures(max_a):
+def _large_fixtures():
     import glob
     import numpy as np
     out = []
     for p in sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "large_actions", "*.npz"))):
         z = np.load(p)
-        if z["root_policy"].shape[-1] <= max_a and int(z["cfg_number_of_player"]) == 1:
+        if int(z["cfg_number_of_player"]) == 1:
             out.append("large_actions/" + os.path.basename(p)[:-4])
     return out
 
 
-@pytest.mark.parametrize("name", _large_fixtures(128))
+@pytest.mark.parametrize("name", _large_fixtures())
 def test_oracle_replays_the_large_action_fixtures(name):
-    """The oracle (oracle/smz_oracle.c, up to 128 actions) against the reference's own large-action searches: the fixtures the
-    GPU tests hold the wave-per-tree kernels to are pinned here as well, with every act output."""
+    """The oracle (oracle/smz_oracle.c, 1 .. 1024 actions) against every single-player large-action search of the reference's,
+    33 to 1024 actions wide: the fixtures the GPU tests hold the wave-per-tree kernels to are pinned here as well, with every
+    act output.  Above 128 actions this is what anchors the oracle's pairwise sums, wide `choice` rounds and Dirichlet draws
+    to the reference; tests/test_gpu_large_actions_oracle.py then holds the kernels to the oracle on every tree."""
     import numpy as np
     import golden_util as gu
     import harness
@@ -91,3 +93,16 @@ def test_oracle_replays_the_large_action_fixtures(name):
             assert action == int(case[k + "_action"]) and root_value == case[k + "_root_value"], (T, A)
             assert np.array_equal(policy, case[k + "_policy"]) and np.array_equal(child_visits, case[k + "_child_visits"]), T
             assert t2.random_sample() == case[k + "_probe"], T
+
+
+def test_oracle_refuses_more_than_1024_actions():
+    """orc_tree_new sizes its stack arrays for 1 .. 1024 actions and sampled children and returns NULL outside that range."""
+    import ctypes as C
+    import orc
+    for A, K in ((1025, 2), (0, 1), (2000, 2000)):
+        with pytest.raises(ValueError):
+            orc.Tree(orc.make_cfg(A, K, 3, 4))
+    pbc = orc.pbc_table(19652, 1.25, 6)
+    for A, K in ((4, 0), (4, 1025), (-1, 2)):                 # (make_cfg clips K to A: the library itself is asked here)
+        assert not orc.lib().orc_tree_new(C.byref(orc.Cfg(A, K, 3, 4, 19652, 1.25, 0.95, 0.25, 0.25)), pbc.ctypes.data_as(C.c_void_p))
+    assert orc.Tree(orc.make_cfg(1024, 1024, 3, 1)).h

@@ -33,7 +33,8 @@ def test_state_roundtrip_matches_numpy():
     assert pos2 == p and np.array_equal(key2, k)
 
 
-@pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 7, 8, 9, 11, 16, 17, 31, 33, 64, 100, 128])
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 7, 8, 9, 11, 16, 17, 31, 33, 64, 100, 128,
+                               129, 130, 136, 137, 255, 256, 257, 264, 513, 1000, 1023, 1024])   # > 128: numpy's pairwise split
 def test_numpy_sum_order(n):
     L = orc.lib()
     rs = np.random.RandomState(n)
@@ -67,6 +68,58 @@ def test_root_expansion_draws_and_dirichlet(A, K, peaked):
         _, pri, _, _ = t.root_stats()
         ref_pri = np.array([p[a] * (1 - 0.25) + ref_noise[a] * 0.25 for a in range(A)])
         assert np.array_equal(pri, ref_pri)
+        assert t.random_sample() == rs.random_sample()
+
+
+WIDE = [(129, 3, 0.3), (200, 200, 0.3), (256, 2, 0.3), (256, 2, 1.0), (256, 2, 0.03), (313, 2, 0.3), (1000, 5, 0.3),
+        (1024, 2, 0.3), (1024, 1024, 0.3)]
+
+
+@pytest.mark.parametrize("A,K,alpha", WIDE)
+def test_wide_root_expansion_draws_and_dirichlet(A, K, alpha):
+    """Above numpy's 128-element summation block, up to the oracle's 1024 actions: the root's choice(A, A, p, replace=False)
+    (rounds of up to A draws, the float32 pairwise sum in p) and dirichlet([alpha] * A) consume numpy's draws and give numpy's
+    noise and float64 priors."""
+    for seed in range(4):
+        for peaked in (False, True):
+            rs = np.random.RandomState(seed)
+            pol = _policy(np.random.RandomState(100 + seed), A, peaked)
+            t = orc.Tree(orc.make_cfg(A, K, 0, 8, alpha=alpha, frac=0.25)); t.seed(seed)
+            noise = t.root_init(pol, train=True)
+            p = (pol + 1e-12); p = p / p.sum()
+            assert list(np.sort(rs.choice(A, A, p=p, replace=False))) == list(range(A))
+            ref_noise = rs.dirichlet([alpha] * A)
+            assert np.array_equal(noise, ref_noise)
+            _, pri, _, _ = t.root_stats()
+            assert np.array_equal(pri, p * np.float32(1 - 0.25) + ref_noise * 0.25)
+            assert np.array_equal(t.dump()["prior"][1:1 + A], p)
+            assert t.random_sample() == rs.random_sample()
+
+
+@pytest.mark.parametrize("A,K", sorted({(A, K) for A, K, _ in WIDE}))
+def test_wide_leaf_expansion_sampled_subset(A, K):
+    """choice(A, K, p, replace=False) with up to 1024 actions and K up to A: the sampled subset, sorted, with un-renormalised
+    priors, and the stream position after it."""
+    for seed in range(4):
+        rs = np.random.RandomState(seed)
+        pr = np.random.RandomState(500 + seed)
+        t = orc.Tree(orc.make_cfg(A, K, 0, 1)); t.seed(seed)
+        root_pol = _policy(pr, A, False)
+        t.root_init(root_pol, train=False)
+        p0 = root_pol + 1e-12; p0 = p0 / p0.sum()
+        rs.choice(A, A, p=p0, replace=False)
+        leaf, parent, act, flag = t.select()
+        rs.uniform(low=1e-7, high=2e-7, size=A)            # one jitter draw per root child, in order
+        assert parent == 0 and flag == 0 and act == leaf - 1
+        pol = _policy(pr, A, seed % 2 == 0)
+        t.expand_backup(pol, 0.5)
+        p = pol + 1e-12; p = p / p.sum()
+        picks = np.sort(rs.choice(A, K, p=p, replace=False))
+        d = t.dump()
+        cb = d["child_base"][leaf]
+        assert cb == 1 + A
+        assert list(d["action"][cb:cb + K]) == list(picks)
+        assert np.array_equal(d["prior"][cb:cb + K], p[picks])
         assert t.random_sample() == rs.random_sample()
 
 

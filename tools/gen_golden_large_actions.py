@@ -6,7 +6,8 @@ reference through oracle/_ref_import.py, as tools/gen_golden_players.py does, so
 Discrete(A) mlp_model (small trunks: the fixtures stay small), and the act outputs at every temperature (post_search).  The GPU
 tests read the committed fixtures under tests/golden/large_actions/ and nothing else.
 
-    python tools/gen_golden_large_actions.py
+    python tools/gen_golden_large_actions.py [NAME ...]      (no name: every fixture; names, of new_fixtures' entries: only those,
+                                                              every other file stays as it is)
 """
 import os
 import sys
@@ -38,6 +39,9 @@ def cases(ref, model, A, K, sims, train, n, seed, **extra):
     return kw, out
 
 
+ONLY = set(sys.argv[1:])
+
+
 def save(name, kw, recs):
     data = G.stack_cases(recs)
     for k, v in kw.items():
@@ -53,6 +57,8 @@ def main():
     ref = R.import_reference()
     torch.set_num_threads(1)
     net = lambda A, seed: G.fresh_mlp(ref, OBS, A, S=8, H=16, L=0, seed=seed)   # noqa: E731
+    if ONLY:
+        return new_fixtures(ref, net)
     save("la_A33_K2_sims50", *cases(ref, net(33, 1), 33, 2, 50, True, 2, 100))            # the first LA-only width
     save("la_A64_K2_sims50_notrain", *cases(ref, net(64, 2), 64, 2, 50, False, 2, 200))
     save("la_A100_K5_sims30", *cases(ref, net(100, 3), 100, 5, 30, True, 2, 300))
@@ -66,6 +72,18 @@ def main():
               maxium_action_sample=2, num_simulations=30, number_of_player=2, custom_loop=None)
     GP.save.__globals__["OUT"] = OUT
     GP.save("la_A64_K2_sims30_p2", kw, GP.search_cases(ref, net(64, 8), _obs(1, 7800), kw, roots=(0, 1)))
+    new_fixtures(ref, net)
+
+
+def new_fixtures(ref, net):
+    """The fixtures added with the oracle's 1024-action range (each is skipped unless named when names are given)."""
+    todo = [("la_A1024_K3_sims12", lambda: cases(ref, net(1024, 9), 1024, 3, 12, True, 2, 800)),        # the action limit
+            ("la_A200_K200_sims12", lambda: cases(ref, net(200, 10), 200, 200, 12, True, 2, 900)),      # K > 128: ragged 96 + 104 split
+            ("la_A129_K3_sims12_alpha1", lambda: cases(ref, net(129, 11), 129, 3, 12, True, 2, 1000,    # gamma(1): two words a round
+                                                       root_dirichlet_alpha=1.0))]
+    for name, make in todo:
+        if not ONLY or name in ONLY:
+            save(name, *make())
 
 
 if __name__ == "__main__":
